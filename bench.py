@@ -7,8 +7,13 @@ data.npoints=8192, seeded random weights -- no checkpoints/datasets offline). In
 before the timed region. With --gpus N (launched by torch.distributed.run) every rank denoises its own
 B patches: patch-level sharding, no data-path collective, weak scaling; time = max over ranks.
 
-Prints ONE JSON line (rank 0) with the driver's fields + "roofline" (dominant kernel, live HIP-event
-timing) + "cpu_baseline" (the CPU oracle timed on this host on a bounded sample, N=1 only).
+Prints ONE JSON line (rank 0) with the driver's fields. A plain run does only what that headline needs: set up, warm up,
+time --steps sample calls, write the outputs if --dump-outputs DIR is given, print. --full adds the other measurements:
+"roofline" (dominant kernel, live HIP-event timing), "alt_math", "train_step", "pvdl" and "cpu_baseline" (the CPU oracle
+timed on this host on a bounded sample, N=1 only); the --no-* flags drop single legs of a --full run.
+
+--dump-outputs DIR writes what the last timed sample call returned (rank 0: x_chain, x_pred, x_start) as float32
+DIR/<name>.npy; inputs and weights are seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -391,10 +396,21 @@ def cpu_baseline(sd, n_points, T, patches=2, budget_s=20.0):
                       + ("" if steps == T else f", extrapolated to T={T}")}
 
 
-def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":  # (a process of cpu_baseline)
-        a = sys.argv[2:]
-        return cpu_worker(a[0], int(a[1]), int(a[2]), int(a[3]), float(a[4]), int(a[5]), int(a[6]))
+def legs(args, world, rank=0, env=os.environ):
+    """the measurements a run adds to its headline line, in the order they run: none in a plain run. With --full, on rank 0:
+    the roofline, and in a one-rank run also the bf16x6 comparison (not when P2PB_CONV_MATH pins the arithmetic), the
+    training step, PVDL and the CPU baseline, each unless its --no-* flag drops it"""
+    if not args.full or rank != 0:
+        return []
+    out = ["roofline"]
+    if world == 1:
+        out += [name for name, skip in (("alt_math", args.no_alt_math or "P2PB_CONV_MATH" in env),
+                                        ("train_step", args.no_train_step), ("pvdl", args.no_pvdl),
+                                        ("cpu_baseline", args.no_cpu_baseline)) if not skip]
+    return out
+
+
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -403,14 +419,26 @@ def main():
     ap.add_argument("--points", type=int, default=8192)
     ap.add_argument("--T", type=int, default=30)
     ap.add_argument("--graph", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-math", action="store_true", help="skip the bf16x6 comparison leg (profiling runs)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the config-3 training-step leg")
-    ap.add_argument("--no-pvdl", action="store_true", help="skip the BASELINE config-4 leg (full-width PVDL, 8 x 50000 points)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, alt-math, training-step, PVDL and CPU-baseline legs (off: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline leg")
+    ap.add_argument("--no-alt-math", action="store_true", help="with --full: skip the bf16x6 comparison leg (profiling runs)")
+    ap.add_argument("--no-train-step", action="store_true", help="with --full: skip the config-3 training-step leg")
+    ap.add_argument("--no-pvdl", action="store_true",
+                    help="with --full: skip the BASELINE config-4 leg (full-width PVDL, 8 x 50000 points)")
     ap.add_argument("--backend", default="nccl", help="process-group backend: nccl (= RCCL over xGMI); gloo only with --dry-run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / timing protocol only, no GPU work (CPU self-test of the N-rank path)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--cpu-worker":  # (a process of cpu_baseline)
+        a = sys.argv[2:]
+        return cpu_worker(a[0], int(a[1]), int(a[2]), int(a[3]), float(a[4]), int(a[5]), int(a[6]))
+    args = parser().parse_args()
     from p2p_bridge_amd import sharding
 
     if args.backend != "nccl" and not args.dry_run:
@@ -473,7 +501,10 @@ def main():
     if world > 1:
         assert res["ranks"]["distinct_devices"] == world, res["ranks"]
     res["config"]["conv_math"] = conv_math_note()
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
+    run = legs(args, world, rank)
+    if "roofline" in run:
         res["roofline"] = gemm_roofline(model, args.batch, args.points)
         res["roofline"]["second_kernel"] = conv_roofline(model, x_start)  # the voxel convolution the sampler runs
         evals = args.T
@@ -481,15 +512,16 @@ def main():
             61.35e9 * args.batch * evals / (dt / args.steps) / 1e12, 2)  # 61.35 GFLOP/sample/eval
         chains = model._sampler_chains(x_start)
         res["roofline"]["hbm_kernels"] = hbm_kernels(args.batch // chains)
-        if world == 1 and "P2PB_CONV_MATH" not in os.environ and not args.no_alt_math:
-            res["alt_math"] = alt_math_leg(cfg, sd, x_start, args)
-        if world == 1 and not args.no_train_step:
-            del model  # (free the sampler's graph pool first)
-            res["train_step"] = train_step_leg()
-        if world == 1 and not args.no_pvdl:
-            res["pvdl"] = pvdl_leg()
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(sd, args.points, args.T)
+    if "alt_math" in run:
+        res["alt_math"] = alt_math_leg(cfg, sd, x_start, args)
+    if "train_step" in run:
+        del model  # (free the sampler's graph pool first)
+        res["train_step"] = train_step_leg()
+    if "pvdl" in run:
+        res["pvdl"] = pvdl_leg()
+    if "cpu_baseline" in run:
+        res["cpu_baseline"] = cpu_baseline(sd, args.points, args.T)
+    if rank == 0:
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.barrier()
@@ -676,6 +708,26 @@ def pvdl_leg(B=8, N=50000, T=30, extra=3, reps=2, fit_batch=64):
                                "frac_of_split_ceiling": round(tff / split_peak_tflops(), 4),
                                "peak_memory_GiB": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1)}
     return res
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out, path):
+    """`sample()`'s return value of the last timed call, every tensor as float32 `path/<key>.npy`. Above 64 MB in all
+    (large --batch / --points) the same fixed, seeded subset of patches is kept in every array."""
+    import numpy as np
+
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in sorted(out.items()) if torch.is_tensor(v)}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        B = next(iter(arrs.values())).shape[0]
+        keep = max(1, int(B * DUMP_LIMIT_BYTES // total))
+        idx = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def result_line(args, world, dt, dist):

@@ -107,3 +107,60 @@ def test_hbm_table_takes_the_newest_round_by_name():
     t = bench.hbm_kernels(16)
     assert t["source"].startswith(f"profiles/{names[-1]} "), t["source"]
     assert any(k["group"].startswith("voxelize") and k["ms_per_eval"] > 0 for k in t["kernels"])
+
+
+def test_dump_outputs_writes_float32_and_caps_the_size(tmp_path, monkeypatch):
+    """--dump-outputs: every tensor of sample()'s return value as float32 DIR/<key>.npy; above the cap the SAME seeded subset
+    of patches is kept in every array, so two runs (or two builds) stay comparable array for array"""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(0)
+    chain = torch.randn(8, 2, 3, 64, generator=g)
+    out = {"x_chain": chain, "x_pred": chain[:, 0], "x_start": torch.randn(8, 3, 64, generator=g).double()}
+    bench.dump_outputs(out, str(tmp_path / "all"))
+    for k, v in out.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 7000)  # room for 2 of the 8 patches (3072 B each over all three arrays)
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    total = 0
+    for k in out:
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.shape[0] == 2 and np.array_equal(a, b)
+        total += a.nbytes
+    assert total <= 7000
+    xc, xp = np.load(tmp_path / "a" / "x_chain.npy"), np.load(tmp_path / "a" / "x_pred.npy")
+    assert np.array_equal(xc[:, 0], xp)  # the same patches in every array
+
+
+def test_plain_run_measures_only_the_headline():
+    """the legs main() runs beside the headline (bench.legs): none in a plain run, all of them under --full, each --no-*
+    flag drops its own leg, ranks other than 0 and multi-rank runs measure no one-rank leg"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    legs = lambda argv, world=1, rank=0, env=None: bench.legs(bench.parser().parse_args(argv), world, rank, env or {})
+    every = ["roofline", "alt_math", "train_step", "pvdl", "cpu_baseline"]
+    assert legs([]) == [] and legs(["--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", "d"]) == []
+    assert legs(["--no-pvdl", "--no-alt-math"]) == []
+    assert legs(["--full"]) == every
+    for flag, leg in (("--no-alt-math", "alt_math"), ("--no-train-step", "train_step"), ("--no-pvdl", "pvdl"),
+                      ("--no-cpu-baseline", "cpu_baseline")):
+        assert legs(["--full", flag]) == [x for x in every if x != leg], flag
+    assert legs(["--full", "--no-cpu-baseline", "--no-alt-math", "--no-train-step", "--no-pvdl"]) == ["roofline"]
+    assert legs(["--full"], env={"P2PB_CONV_MATH": "bf16x6"}) == [x for x in every if x != "alt_math"]
+    assert legs(["--full"], world=2) == ["roofline"] and legs(["--full"], world=2, rank=1) == []
+
+
+def test_result_line_fields():
+    """the headline fields the driver reads, on the line of a run (dry run: the same result_line())"""
+    r = _run(["--gpus", "1", "--backend", "gloo", "--dry-run", "--steps", "2", "--warmup", "0"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(res)
+    assert res["steps"] == 2 and res["ms_per_step"] > 0

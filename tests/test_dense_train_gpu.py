@@ -78,7 +78,8 @@ def test_conv3d_backward_under_every_conv_math(conv_math):
     form -- under P2PB_CONV_MATH=fp32 the backward used to raise. Forward + both gradients vs fp64 under each arithmetic."""
     from p2p_bridge_amd import dense, fused
 
-    prev = fused.set_conv_math(conv_math)
+    prev = fused._conv_math_override  # (set_conv_math returns the resolved name: restoring that would pin it process-wide)
+    fused.set_conv_math(conv_math)
     try:
         torch.manual_seed(5)
         conv = nn.Conv3d(64, 32, 3, padding=1).cuda()
