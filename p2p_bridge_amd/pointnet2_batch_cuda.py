@@ -11,7 +11,7 @@ import torch
 
 from . import _experiment
 
-from ._lib import call, check, lib, ptr, stream_ptr
+from ._lib import P2PBError, call, check, lib, ptr, stream_ptr
 
 _i, _f = ctypes.c_int, ctypes.c_float
 F32, I32 = torch.float32, torch.int32
@@ -84,8 +84,17 @@ def trilinear_devoxelize_backward(grad_y, indices, weights, r):
     b, c, n = grad_y.shape
     r3 = int(r) ** 3
     gx = torch.empty(b, c, r3, dtype=F32, device=grad_y.device)
-    call("p2pb_trilinear_devoxelize_backward", _i(b), _i(c), _i(n), _i(r3), ptr(indices), ptr(weights), ptr(grad_y),
-         ptr(gx), stream_ptr())
+    try:
+        call("p2pb_trilinear_devoxelize_backward", _i(b), _i(c), _i(n), _i(r3), ptr(indices), ptr(weights), ptr(grad_y),
+             ptr(gx), stream_ptr())
+    except P2PBError as e:
+        if not lib().p2pb_get_deterministic():
+            raise
+        # (the library refuses a grid row beyond the LDS -- csrc/common.h SCAT_LDS_MAX, scat_rows -- in deterministic mode: only
+        #  the global-atomic kernel, whose order is not fixed, would be left)
+        raise P2PBError(f"trilinear_devoxelize_backward: no deterministic kernel for r = {r} (r^3 = {r3} voxels per grid row, "
+                           "beyond what the fixed-order kernel holds in LDS): train this resolution outside "
+                           "p2p_bridge_amd.deterministic()") from e
     return gx
 
 

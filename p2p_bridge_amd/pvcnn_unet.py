@@ -356,6 +356,9 @@ class SharedMLP(nn.Module):
         from . import fused
 
         if fused.enabled(self, x):
+            # (PVConv's dense fallback hands its SE gate here too; `dropout` is inert: the fused form runs in eval mode only)
+            if rgate is not None:
+                residual = residual * rgate.unsqueeze(-1)
             return self._run_fused(x, cond, reduce_max, residual)
         from . import dense
 
@@ -531,7 +534,7 @@ class PVConv(nn.Module):
     def forward(self, data: PVCData) -> PVCData:
         coords, features, cond = data.coords, data.features, data.cond
         assert features.shape[0] == coords.shape[0] and features.shape[2] == coords.shape[2] and coords.shape[1] == 3
-        if not self.training and not torch.is_grad_enabled() and self.resolution in (4, 8, 16, 32):
+        if not self.training and not torch.is_grad_enabled() and self.resolution in FUSED_RESOLUTIONS:
             pf = self.point_features.layers
             if len(pf) == 3 and features.is_cuda:  # one conv -> norm -> Swish: joined to the voxel branch in one pass
                 from . import fused as F_
@@ -578,6 +581,9 @@ class PVConv(nn.Module):
         if self.attn is not None:  # models/pvcnn.py:327-328
             data.features = self.attn(data.features)
         return data
+
+
+FUSED_RESOLUTIONS = (4, 8, 16, 32)  # the fused inference branch's grids; any other resolution takes the dense path above
 
 
 def compact_plan():
@@ -896,15 +902,18 @@ class Geometry:
 
         def voxel_prep(i, c, stream):
             # per (level, resolution): voxel coordinates, occupancy + sorted point lists, brick lists of the sparse convolutions --
-            # coordinate-only, shared by every PVConv of the level
+            # coordinate-only, shared by every PVConv of the level; only for the resolutions of the fused branch (the others
+            # voxelise inside PVConv's dense fallback)
             for (r, normalize, eps) in vox_plan.get(i, ()):
+                if r not in FUSED_RESOLUTIONS:
+                    continue
                 vcoords, vox = L.voxel_coords(c, r, normalize, eps)
                 cnt, ws = fused.voxel_sort(vox, r)
                 lists = counts = None
                 c1, c2 = compact_plan()
                 if r in c1 or r in c2:
                     lists, counts = fused.active_lists(cnt, r)
-                elif r >= 32:
+                elif r == 32:  # (the brick-list sparse convolutions: _voxel_branch_fused)
                     lists, counts = fused.brick_lists(cnt, r)
                 ev = torch.cuda.Event()
                 ev.record(stream)

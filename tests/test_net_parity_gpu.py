@@ -151,6 +151,38 @@ def test_pvdl_like_topology(tiny):
     assert (out_train - ref).abs().max().item() < TOL
 
 
+@pytest.mark.parametrize("vres", [[32, 16, 8, 4], [12, 6, 6, 2], [64, 32, 16, 8]], ids=lambda v: "r" + "-".join(map(str, v)))
+def test_voxel_resolutions(tiny, vres):
+    """The tiny network (8..128 channels) at other voxel resolutions, seeded weights shared by both sides, fused inference and
+    training-mode forward vs the oracle. [32, 16, 8, 4]: the compact r = 16 and brick-list sparse r = 32 convolutions at narrow
+    channel counts, through the geometry stream and the pre-split operands; [12, 6, 6, 2]: resolutions outside {4, 8, 16, 32}
+    (PVConv's dense fallback, whose SE gate the fused point branch used to drop); [64, 32, 16, 8]: r = 64 (the reference's
+    voxel_resolution_multiplier = 2 on PVDS), where the geometry stream used to ask for brick lists it has none for."""
+    import copy
+
+    from p2p_bridge_amd import p2pb as product
+    from p2p_bridge_amd.pvcnn_unet import PVCNN2Unet
+
+    cfg = copy.deepcopy(tiny[0])
+    cfg["model"]["PVD"]["voxel_resolutions"] = list(vres)
+    cfg["gpu"] = "cpu"
+    torch.manual_seed(0)
+    sd = {k: v.clone() for k, v in PVCNN2Unet(cfg).state_dict().items()}
+    x, _ = net_ref.synthetic_patches(2, 1024, seed=3)
+    t = torch.tensor([10.0, 500.0])
+    model = product.build_model(cfg, sd, device="cuda")
+    model.eval()
+    orc = net_ref.RefNet(cfg, sd, vox_mode="tree")
+    with torch.no_grad():
+        out = model.model(x.cuda(), t.cuda()).cpu()
+        ref = orc(x, t)
+    assert out.shape == ref.shape == (2, 3, 1024)
+    assert (out - ref).abs().max().item() < TOL
+    model.model.train()
+    out_train = model.model(x.cuda(), t.cuda()).detach().cpu()
+    assert (out_train - ref).abs().max().item() < TOL
+
+
 def test_odd_point_counts(tiny):
     """N = 1000 (centres 250 / 62 / 15 / 3): rows that are not 16-byte multiples take the fallback paths of the fused
     kernels (one-position-per-lane GEMM, two-pass pooling, channel-major gathers) -- same contract."""
