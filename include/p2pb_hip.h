@@ -30,12 +30,13 @@ extern "C" {
 
 #define P2PB_EINVAL (-22)
 
-/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (6: round 6 -- since 1:
- * p2pb_debug_gn_finisher removed, flag bit 5 of p2pb_conv3d_k3_forward_sparse, arithmetic code 3 in
- * p2pb_set_split_terms_thread, p2pb_group_sub_stats*, p2pb_se_gate_*, p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
+/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (8: p2pb_softmax_attention_*
+ * added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
+ * p2pb_conv3d_k3_forward_sparse, arithmetic code 3 in p2pb_set_split_terms_thread, p2pb_group_sub_stats*, p2pb_se_gate_*,
+ * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
  * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
-#define P2PB_ABI_VERSION 7
+#define P2PB_ABI_VERSION 8
 
 /* library / device info --------------------------------------------------------------------- */
 int p2pb_version(void);            /* == P2PB_ABI_VERSION of the header the library was built from */
@@ -532,6 +533,21 @@ int p2pb_linear_attention_forward(int b, int heads, int dim_head, int n, const f
                                   void *stream);
 int p2pb_linear_attention_backward(int b, int heads, int dim_head, int n, const float *qkv, const float *ctx,
                                    const float *grad_out, float *grad_qkv, void *stream);
+
+/* Softmax attention core (models/modules.py:197-264 Attention(norm=False, flash=True): `attention_type: flash`), the part
+ * between to_q / to_kv and to_out. Channel-major like everything at this boundary: q f32[b, heads*dim_head, n];
+ * kv f32[b, 2*heads*dim_head, n] in channel order (k | v) x heads x dim_head; dim_head must be 32 (P2PB_EINVAL otherwise).
+ *   out[b, h*32 + d, i] = sum_j softmax_j((q_i . k_j) * 32^-0.5) v[d, j]       f32[b, heads*32, n]   (no mask, no dropout)
+ *   lse[b, h, i]        = log sum_j exp((q_i . k_j) * 32^-0.5)                 f32[b, heads, n]
+ * lse is optional in forward (NULL when no gradient is needed) and required by backward, which recomputes the
+ * probabilities from it. Any n >= 1: keys / values are streamed in tiles with a running max / sum, nothing of size n^2 is
+ * stored. fp32 throughout; no atomics -- the same inputs give the same bits in both directions.
+ * backward: grad_out f32[b, heads*32, n] -> grad_q (q's shape), grad_kv (kv's shape); two launches on `stream`. */
+int p2pb_softmax_attention_forward(int b, int heads, int dim_head, int n, const float *q, const float *kv, float *out,
+                                   float *lse, void *stream);
+int p2pb_softmax_attention_backward(int b, int heads, int dim_head, int n, const float *q, const float *kv,
+                                    const float *out, const float *lse, const float *grad_out, float *grad_q,
+                                    float *grad_kv, void *stream);
 
 /* ---- training: the squeeze-excite gate (csrc/normact.hip) ---------------------------------------------------------------
  * SE3d of the reference (models/modules.py:362-378): gate = sigmoid(W2 relu(W1 mean)); mean f32[b,c] = per-channel mean of the

@@ -201,6 +201,84 @@ class LinearAttention(nn.Module):
         return dense.pointwise(out.unsqueeze(-1), self.to_out).squeeze(-1)
 
 
+class _SoftmaxAttentionCore(torch.autograd.Function):
+    """out_i = sum_j softmax_j(q_i . k_j / sqrt(32)) v_j per (sample, head) on channel-major q [B, heads*32, n] and
+    kv [B, 2*heads*32, n] (k | v) -- csrc/attention.hip softmax_attention_*: the rearranges + scaled_dot_product_attention
+    of models/modules.py:254-263 in both directions, keys streamed through LDS (nothing of size n^2), no atomics"""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads):
+        from ._lib import call, check, ptr, stream_ptr
+        import ctypes
+
+        q, kv = q.contiguous(), kv.contiguous()
+        check(q, torch.float32, "q")  # (raw pointers go to the kernel: device, dtype and layout are checked here)
+        check(kv, torch.float32, "kv")
+        b, c, n = q.shape
+        if c % heads or tuple(kv.shape) != (b, 2 * c, n) or kv.device != q.device:
+            raise RuntimeError(f"q {tuple(q.shape)} / kv {tuple(kv.shape)}: expected [B, heads*32, n] and [B, 2*heads*32, n] "
+                               f"with heads = {heads}")
+        need = any(ctx.needs_input_grad[:2])
+        out = torch.empty_like(q)
+        lse = torch.empty(b, heads, n, dtype=q.dtype, device=q.device) if need else None
+        call("p2pb_softmax_attention_forward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(c // heads), ctypes.c_int(n),
+             ptr(q), ptr(kv), ptr(out), ptr(lse), stream_ptr())
+        if need:
+            ctx.save_for_backward(q, kv, out, lse)
+            ctx.heads = heads
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from ._lib import call, check, ptr, stream_ptr
+        import ctypes
+
+        q, kv, out, lse = ctx.saved_tensors
+        b, c, n = q.shape
+        heads = ctx.heads
+        g = g.contiguous()
+        check(g, torch.float32, "grad_out")
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        call("p2pb_softmax_attention_backward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(c // heads), ctypes.c_int(n),
+             ptr(q), ptr(kv), ptr(out), ptr(lse), ptr(g), ptr(dq), ptr(dkv), stream_ptr())
+        return dq, dkv, None
+
+
+class Attention(nn.Module):
+    """full softmax attention over the tokens, the reference's `Attention(dim, norm=False, flash=True, heads=...)`
+    (models/modules.py:197-264; `attention_type: flash`, models/unet_pvc.py:98-99): bias-free Linears to_q / to_kv / to_out
+    with the reference's names and shapes, no norm, no residual. The reference transposes [B,C,n] -> [B,n,C] around it
+    (unet_pvc.py:239-241); here the tensor stays channel-major: a Linear on [B,n,C] is a 1x1 convolution on [B,C,n] with the
+    same 2-D weight, so the three projections are the pointwise GEMM kernels (which read `.weight` / `.bias` of the layer
+    they are given and cache their weight packs on it) and the core between them is csrc/attention.hip."""
+
+    def __init__(self, dim, heads=4, dim_head=32):
+        super().__init__()
+        self.heads = heads
+        hidden = dim_head * heads
+        self.to_q = nn.Linear(dim, hidden, bias=False)
+        self.to_kv = nn.Linear(dim, hidden * 2, bias=False)
+        self.to_out = nn.Linear(hidden, dim, bias=False)
+
+    def forward(self, x):
+        from . import fused
+        from ._lib import check
+
+        x = x.contiguous()
+        check(x, torch.float32, "x")  # (no eager form of the projections: a host or half tensor is refused here)
+        if fused.enabled(self, x):
+            q, _ = fused.pw_conv(x, self.to_q, stats=False, use_bias=False)
+            kv, _ = fused.pw_conv(x, self.to_kv, stats=False, use_bias=False)
+            out = _SoftmaxAttentionCore.apply(q, kv, self.heads)
+            return fused.pw_conv(out, self.to_out, stats=False, use_bias=False)[0]
+        from . import dense
+
+        if not dense.enabled(x):
+            raise RuntimeError("Attention: the HIP training kernels are switched off and there is no eager form")
+        out = _SoftmaxAttentionCore.apply(dense.pointwise(x, self.to_q), dense.pointwise(x, self.to_kv), self.heads)
+        return dense.pointwise(out, self.to_out)
+
+
 class StyleBank:
     """All AdaGN style vectors of one network evaluation from ONE GEMM: every AdaGN owns a
     Linear(cond_dim -> 2C) on the same global embedding (models/modules.py:337,345), 42 (PVDS) / 57 (PVDL)
@@ -1022,10 +1100,20 @@ class PVCNN2Unet(nn.Module):
         self.plan = plan
         cd = self.cond_emb_dim
         attn_type = str(_get(pvd, "attention_type", "linear")).lower()
-        if attn_type != "linear":
-            raise NotImplementedError(f"attention_type={attn_type!r}: only 'linear' (LinearAttention, every shipped "
-                                      "config) is built; 'flash' (models/modules.py Attention) is off the hot path")
-        attn_fn = lambda dim: LinearAttention(dim, heads=heads)
+        # models/unet_pvc.py:96-101: LinearAttention | Attention(norm=False, flash=True) | anything else: no attention at all
+        if attn_type == "linear":
+            attn_fn = lambda dim: LinearAttention(dim, heads=heads)
+        elif attn_type == "flash":
+            attn_fn = lambda dim: Attention(dim, heads=heads)
+        else:
+            attn_fn = None
+        if attn_type != "linear" and any(s.get("attn") for st in plan["sa"] for s in st["convs"]):
+            # the reference hands a PVConv's [B,C,N] features to the attention as they are (models/pvcnn.py:329-330): its
+            # `Attention` then applies Linear(C) along the POINT axis (runs only if N == C, and means nothing), and with no
+            # attention type it calls None(out_channels) while building -- there is no behaviour to mirror
+            raise ValueError(f"attention_type={attn_type!r} with model.PVD.attentions={list(_get(pvd, 'attentions'))}: a PVConv-"
+                             "level attention (a flag on a stage that has a PVConv) exists for attention_type 'linear' only; "
+                             "flag only the last stage (the stock [0, 0, 0, 1])")
         pv = lambda s: PVConv(s["cin"], s["cout"], s["r"], with_se=with_se, dropout=dropout, cond_dim=cd,
                               attention=attn_fn if s.get("attn") else None)
         sa_layers = []
@@ -1041,7 +1129,7 @@ class PVCNN2Unet(nn.Module):
             for blk in (stage if isinstance(stage, _Stage) else [stage]):
                 if isinstance(blk, PVConv):
                     blk.level = i  # works on the stage's input coordinates
-        self.global_att = attn_fn(plan["bottleneck"])
+        self.global_att = attn_fn(plan["bottleneck"]) if attn_fn is not None else None
         fp_layers = []
         for st in plan["fp"]:
             blocks = [PointNetFPModule(st["mlp_in"], st["mlp_out"], cond_dim=cd)] + [pv(s) for s in st["convs"]]
@@ -1178,7 +1266,8 @@ class PVCNN2Unet(nn.Module):
                 cut += cond.cut  # (the embedding as the decoder's style Linears see it: StyleBank.evaluate_train)
             self.cut = [x for x in cut if x.requires_grad]
 
-        data.features = self.global_att(data.features)
+        if self.global_att is not None:  # (attention_type neither linear nor flash: the bottleneck passes through)
+            data.features = self.global_att(data.features)
 
         for j, stage in enumerate(self.fp_layers):
             ltemb = None
