@@ -2,8 +2,9 @@
 
     python -m p2p_bridge_amd.build [--force]
 
-hipcc cross-compiles without a GPU. One object per .hip (conv3d.hip: two, built in parallel -- its header) so edits rebuild
-in seconds to minutes; a build from scratch takes about 2.5 minutes on 8 cores.
+hipcc cross-compiles without a GPU. One object per .hip, no source compiled twice, so edits rebuild in seconds to minutes
+(the three arithmetics of the split voxel convolution are three small .hip files around shared headers: csrc/conv3d_common.h);
+a build from scratch takes about 2 minutes on 8 cores.
 -ffp-contract=off: every fused multiply-add is spelled __fmaf_rn in the sources (arithmetic contract,
 DESIGN.md); the compiler must not invent others. -munsafe-fp-atomics: fp32 atomicAdd -> one
 global_atomic_add_f32 instead of a CAS loop.
@@ -23,10 +24,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics",
          "-Wall", "-Wno-unused-function"]
 
-
-# conv3d.hip is three translation units (its header): the second holds the bf16x6 instantiations of the split kernels, the third
-# the bf16x3 ones of the training data gradient
-EXTRA_UNITS = {"conv3d.hip": [("_bf16x6", ["-DCONV_TU=6"]), ("_bf16x3", ["-DCONV_TU=3"])]}
+# the long compiles (minutes each), started first so that the short ones fill in around them
+SLOW = ("conv3d.hip", "conv3d_bf16x6.hip", "conv3d_fp32.hip", "pointwise.hip", "conv3d_bf16x3.hip")
 
 
 def _newer(a, bs):
@@ -44,12 +43,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         objs.append(o)
         if force or _newer(o, [s] + hdrs):
             jobs.append([HIPCC] + FLAGS + ["-c", s, "-o", o])
-        for tag, defs in EXTRA_UNITS.get(os.path.basename(s), ()):  # the same source compiled again with other macros
-            o = os.path.join(OBJ, os.path.basename(s)[:-4] + tag + ".o")
-            objs.append(o)
-            if force or _newer(o, [s] + hdrs):
-                jobs.append([HIPCC] + FLAGS + defs + ["-c", s, "-o", o])
-    jobs.sort(key=lambda j: 0 if "conv3d" in j[-3] else 1)  # the two long compiles first
+    jobs.sort(key=lambda j: SLOW.index(os.path.basename(j[-3])) if os.path.basename(j[-3]) in SLOW else len(SLOW))
 
     def run(cmd):
         if verbose:

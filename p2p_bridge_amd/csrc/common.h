@@ -44,7 +44,7 @@ __device__ __forceinline__ float halfwave_sum_to_last(float v) {
   return v;
 }
 
-// ---- fp32 operands on the bf16 matrix pipe (conv3d.hip "split-operand form", pointwise.hip) ----
+// ---- fp32 operands on the bf16 matrix pipe (conv3d_split.h "split-operand form", pointwise.hip) ----
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -131,25 +131,8 @@ __device__ __forceinline__ float f16_weight_scale(float wmax) {
   (void)frexpf(wmax, &e);  // wmax = m * 2^e, m in [0.5, 1)
   return ldexpf(1.0f, 14 - e);
 }
-// max |w| of a tensor into *slot (uint bits of a non-negative float order like the float), slot zeroed before
-static __global__ void absmax_bits_kernel(const float *__restrict__ w, size_t n, unsigned *__restrict__ slot) {
-  __shared__ float part[4];
-  float m = 0.0f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-  __syncthreads();
-  // one atomic per workgroup (they serialise on the one line: 256 of them were most of this kernel's 10 us)
-  if (threadIdx.x == 0) atomicMax(slot, __builtin_bit_cast(unsigned, fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]))));
-}
-// workgroups for a tensor of n elements: 16 elements per thread, at most 64
-static inline unsigned absmax_blocks(size_t n) {
-  const size_t b = (n + 4095) / 4096;
-  return (unsigned)(b < 1 ? 1 : b > 64 ? 64 : b);
-}
-
 // ---- GroupNorm(+AdaGN) finisher: the {sum, sum of squares} partials of a producing kernel -> per-(sample, channel) scale / shift ----
-// (the arithmetic of gn_affine_kernel, conv3d.hip, which calls this too: one workgroup, >= 256 threads of it, per (sample, group);
+// (the arithmetic of gn_affine_kernel, pvconv_finish.hip, which calls this too: one workgroup, >= 256 threads of it, per (sample, group);
 //  fixed summation order, double accumulation: the same bits whichever kernel runs it.) Callers: gn_affine_kernel -- also the launch
 // that pointwise.hip puts behind a producer whose caller armed a finisher (p2pb_gn_finisher_arm) -- and the small kernels that fold
 // the norm into their own prologue (far_field_kernel, pvconv_tail_kernel, minmax_act_pool_kernel). Round 4's forms that ran it in
@@ -162,6 +145,10 @@ struct GnFinish {
   int style_stride, groups;
   float eps;
 };
+// (host) the shapes the finisher takes: whole groups of at most 256 channels, style rows that hold factor and bias
+static inline bool gn_shape_ok(int c, int groups, const float *style, int style_stride) {
+  return groups > 0 && c % groups == 0 && c / groups <= 256 && !(style && style_stride < 2 * c);
+}
 typedef float gnf_f32x2 __attribute__((ext_vector_type(2)));
 // lds: 4 x 256 doubles per 256-thread SLICE. Every thread of the workgroup calls it (same barriers); a slice is 256 consecutive
 // threads with vt = the thread's index inside it, `live` = the slice has a group to finish (a 1024-thread workgroup finishes four
@@ -420,7 +407,7 @@ enum {
 };
 void p2pb_note_pointwise_form(int cin, int cout, int npos, int form);
 // the GroupNorm finisher armed for this thread's next statistics-producing launch (abi.hip) and the launch that runs it behind
-// the producer (conv3d.hip)
+// the producer (pvconv_finish.hip)
 bool p2pb_gn_finisher_take(GnFinish *out);
 int p2pb_gn_affine_launch(int b, int c, int nslots, const float *part, const GnFinish &f, hipStream_t s);
 

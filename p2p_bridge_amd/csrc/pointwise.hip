@@ -14,6 +14,7 @@
 // (so stores are lane-consecutive), K = input channels. Small-C layers are HBM-bound (8 FLOP/B at
 // C=32..64), the wide ones (Pnet2Stage 512->1024) MFMA-bound.
 #include "common.h"
+#include "absmax.h"
 #include <atomic>
 #include <stdint.h>
 #include <stdlib.h>
@@ -22,7 +23,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define PW_CK 16  // input channels per register stage (2 sub-chunks of 8): 3 waves/SIMD stay resident (32 -> 2)
 
-// Swish on the hardware exp2 / reciprocal units (see conv3d.hip fast_swish for the error budget)
+// Swish on the hardware exp2 / reciprocal units (see conv3d_common.h fast_swish for the error budget)
 __device__ __forceinline__ float swishf(float v) {
   return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.44269504088896340736f));
 }
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void pw_wide_kernel(int cin, int cout, int 
   const int pc = pok ? p : P - 4;  // clamped lanes multiply garbage that is never stored
   const float *inb = in + (size_t)b * cin * P;
   // bias (+ per-sample bias) of the workgroup's channels through LDS: fetched from global memory inside the epilogue's row
-  // loops they were one serialised L2 round trip per row (conv3d.hip, tools/exp_conv_timeline.py)
+  // loops they were one serialised L2 round trip per row (conv3d_split.h, tools/exp_conv_timeline.py)
   __shared__ float pww_bias[32 * MT];
   if (tid < 32 * MT) {
     const int co = co0 + tid;
@@ -645,7 +646,7 @@ extern "C" size_t p2pb_pointwise_stats_floats(int b, int cout, int npos) {
 // ------------------------------------------------------------------------------------------------
 // Split-operand form of the same GEMM for the matrix-bound layers (wide channel counts): fp32 operands as
 // three bf16 terms, six bf16 MFMA products per fp32 product, fp32 accumulate -- the arithmetic of
-// conv3d.hip's split kernel (fp32-faithful: dropped terms < 2^-26 |x*w|), 2.67x fewer matrix cycles.
+// conv3d_split.h's split kernel (fp32-faithful: dropped terms < 2^-26 |x*w|), 2.67x fewer matrix cycles.
 // At that rate the operands can no longer stream through per-lane global loads (the wide kernel above
 // would need ~50 B/clk/CU of L1 bandwidth), so this one is the classic LDS-tiled GEMM:
 //   workgroup = 4 waves as 2 (M) x 2 (N): 128 output channels x 128 positions, 32 input channels per stage;
@@ -677,7 +678,7 @@ __device__ __forceinline__ void pws_epilogue(f32x16 (&acc)[2][2 * NB], int b, in
                                              float *__restrict__ mm_out, int pool_u, int out_pm, const float *sb) {
   // sb: the workgroup's bias (+ per-sample bias) values [64 WM], staged in LDS by the kernel's prologue. Fetched from
   // global memory inside the row loops below they were one L2 round trip each, serialised by the loops' branches (the
-  // same finding as in the convolutions' epilogue, conv3d.hip / tools/exp_conv_timeline.py).
+  // same finding as in the convolutions' epilogue, conv3d_split.h / tools/exp_conv_timeline.py).
 #pragma unroll
   for (int pb = 0; pb < NB; ++pb) {  // the wave's NB blocks of 64 positions (even / odd tiles 2 pb, 2 pb + 1)
   const int p = pblk + 128 * pb + 2 * (wn * 32 + l31);

@@ -397,7 +397,7 @@ __global__ __launch_bounds__(256) void vox_gather_cl_occ_kernel(int c, int n, in
   }
 }
 
-// The grid straight in the pre-split operand format of the voxel convolutions (conv3d.hip "S format"): out
+// The grid straight in the pre-split operand format of the voxel convolutions (conv3d_split.h "S format"): out
 // u32x4[b][r^3][ceil(c/16)][2 planes][2 khalf], the fp16 pair (h0 | h1) of 4 x mean for channels chunk*16 + khalf*8 + i --
 // 4 bytes per (voxel, channel) like the fp32 grid, channels padded with zeros to a multiple of 16. A thread owns 8
 // consecutive channels of one voxel; same means (ascending point order) as the kernels above, then the split the

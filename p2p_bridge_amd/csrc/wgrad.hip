@@ -6,7 +6,7 @@
 //   1x1 convolution:     dW[co][ci]      = sum_{b, p} dY[b, co, p] * X[b, ci, p]
 //   both:                db[co]          = sum_{b, p} dY[b, co, p]
 //
-// (The data gradients need no kernel of their own: dX of the 3x3x3 convolution is the forward kernel of conv3d.hip
+// (The data gradients need no kernel of their own: dX of the 3x3x3 convolution is the forward kernel of conv3d_split.h
 // run on dY with the taps flipped and the channel roles swapped, dX of a 1x1 layer is the forward GEMM of
 // pointwise.hip with the transposed weight -- p2p_bridge_amd/dense.py.)
 //

@@ -348,7 +348,7 @@ def conv3d_far_field_gn(prev_bias, conv, part, fin, swish=True):
 
 
 def pvconv_tail(part2, fin2, se=None, point=None):
-    """the tail of a PVConv's voxel branch in one launch (csrc/conv3d.hip pvconv_tail_kernel): part2 = the second convolution's
+    """the tail of a PVConv's voxel branch in one launch (csrc/pvconv_finish.hip pvconv_tail_kernel): part2 = the second convolution's
     statistics partials f32[B,nslots,C,2], fin2 its norm (norm_fin), se = (fc1 weight [hidden, C], fc2 weight [C, hidden]) | None,
     point = (partials of the point branch's 1x1 convolution, its norm_fin) | None ->
     (aff_a, aff_b f32[B,C] = the folded norm x the SE3d gate, scale_p, shift_p f32[B,Cp] | None, None)"""

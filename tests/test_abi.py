@@ -37,7 +37,7 @@ def test_library_contains_gfx950_code_object():
 
 
 def test_no_kernel_issues_ds_write_b96():
-    """Round 4's cross-stream corruption sat in a kernel whose LDS staging the compiler had merged into
+    """Round 4's cross-stream corruption (docs/history/DESIGN_round5.md, section 3.5) sat in a kernel whose LDS staging the compiler had merged into
     ds_write_b96 + ds_write2_b32; the mechanism is unexplained (barrier and s_waitcnt were in order in the ISA), so the invariant
     that protects the library is enforced here: the disassembly of every translation unit of libp2pb_hip.so holds no 12-byte LDS
     store. (tests/test_concurrency_gpu.py is the dynamic half of the net.)"""
