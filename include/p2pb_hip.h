@@ -30,13 +30,13 @@ extern "C" {
 
 #define P2PB_EINVAL (-22)
 
-/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (8: p2pb_softmax_attention_*
- * added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
+/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (9: the set metrics
+ * p2pb_pairwise_chamfer / p2pb_pairwise_emd / p2pb_occupancy_* added; 8: p2pb_softmax_attention_* added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
  * p2pb_conv3d_k3_forward_sparse, arithmetic code 3 in p2pb_set_split_terms_thread, p2pb_group_sub_stats*, p2pb_se_gate_*,
  * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
  * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
-#define P2PB_ABI_VERSION 8
+#define P2PB_ABI_VERSION 9
 
 /* library / device info --------------------------------------------------------------------- */
 int p2pb_version(void);            /* == P2PB_ABI_VERSION of the header the library was built from */
@@ -646,6 +646,35 @@ int p2pb_optim_clip_adam_step(int nchunks, const void *table, const int *chunks,
 int p2pb_conv3d_k3_pack_weights_split_amax(int cout, int cin, const float *w, void *wt_split, const unsigned *amax_bits,
                                            void *stream);
 int p2pb_pointwise_pack_weights_split_amax(int cout, int cin, const float *w, void *wp, const unsigned *amax_bits, void *stream);
+
+/* ---- set-against-set generative metrics (metrics/evaluation_metrics_fast.py; csrc/setmetrics.hip) ----
+ * A f32[s,n,3], B f32[r,m,3] are two SETS of clouds; out f32[s,r] gets one distance per pair (A_i, B_j). The reference builds
+ * such a matrix row by row from an expanded copy of one cloud (_pairwise_EMD_CD_sub :209-231, _pairwise_EMD_CD_ :262-281);
+ * here pairs are indexed inside the kernels and no copy of either set is made.
+ *
+ * p2pb_pairwise_chamfer: out[i,j] = mean_p min_q |A_ip - B_jq|^2 + mean_q min_p |A_ip - B_jq|^2, what :219-228 assembles from
+ * chamfer_3DDist_nograd (dl.mean(dim=1) + dr.mean(dim=1)). The per-point minima are the fp32 numbers of p2pb_chamfer_forward;
+ * each direction's sum is taken in fp64 in a fixed order and the entry is rounded to fp32 once (run-to-run deterministic).
+ * A == B with s == r, n == m is the symmetric case: each directional sum is computed once and out equals its transpose bitwise.
+ * ws: p2pb_pairwise_chamfer_ws_bytes(s, r) bytes. s, r <= 65535. */
+size_t p2pb_pairwise_chamfer_ws_bytes(int s, int r);
+int p2pb_pairwise_chamfer(int s, int r, int n, int m, const float *A, const float *B, float *out, void *ws, void *stream);
+/* p2pb_pairwise_emd: out[i,j] = earth_mover_distance_nograd(A_i, B_j) = approxmatch match cost / n (:230,
+ * PyTorchEMD/emd_nograd.py:13-14,43; cuda/emd_kernel.cu:33,211). The match matrix is never stored: its cost is accumulated
+ * level by level. Not symmetric in its arguments: every entry is computed. Pairs run in chunks of ws_bytes / ((3 n + 2 m) * 4)
+ * (at least one pair must fit, else P2PB_EINVAL); p2pb_pairwise_emd_ws_bytes is the size past which more does not help. */
+size_t p2pb_pairwise_emd_ws_bytes(int s, int r, int n, int m);
+int p2pb_pairwise_emd(int s, int r, int n, int m, const float *A, const float *B, float *out, void *ws, size_t ws_bytes,
+                      void *stream);
+/* p2pb_occupancy_counts: the inner loop of entropy_of_occupancy_grid (:587-600). pts f32[clouds,npts,3]; every point goes to
+ * its nearest centre of the resolution^3 unit-cube grid (unit_cube_grid_point_cloud :534-552; with clip_sphere only the cells
+ * whose centre norm is <= 0.5, numbered in row-major order after the clip). counters i32[G] counts points, bernoulli i32[G]
+ * counts clouds that touch the cell; G = p2pb_occupancy_grid_cells(resolution, clip_sphere) (host arithmetic only; < 0 for a
+ * bad resolution). Integer atomics only: deterministic. 2 <= resolution <= 80, G > 0; ws: p2pb_occupancy_ws_bytes(resolution). */
+int p2pb_occupancy_grid_cells(int resolution, int clip_sphere);
+size_t p2pb_occupancy_ws_bytes(int resolution);
+int p2pb_occupancy_counts(int clouds, int npts, int resolution, int clip_sphere, const float *pts, int *counters,
+                          int *bernoulli, void *ws, void *stream);
 
 #ifdef __cplusplus
 }

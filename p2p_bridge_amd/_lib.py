@@ -35,9 +35,11 @@ SYMBOLS = [
     "p2pb_conv3d_k3_pack_weights_split_adjoint", "p2pb_pointwise_pack_weights_adjoint", "p2pb_pointwise_pack_weights_split_adjoint",
     "p2pb_conv3d_k3_pack_weights_split_amax", "p2pb_pointwise_pack_weights_split_amax",
     "p2pb_se_gate_forward", "p2pb_se_gate_backward", "p2pb_row_max_forward", "p2pb_row_max_backward",
+    "p2pb_pairwise_chamfer_ws_bytes", "p2pb_pairwise_chamfer", "p2pb_pairwise_emd_ws_bytes", "p2pb_pairwise_emd",
+    "p2pb_occupancy_grid_cells", "p2pb_occupancy_ws_bytes", "p2pb_occupancy_counts",
 ]
 
-ABI_VERSION = 8  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
+ABI_VERSION = 9  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
 
 _lib = None
 
@@ -74,6 +76,9 @@ def lib():
         _lib.p2pb_approxmatch_temp_floats.restype = ctypes.c_size_t
         _lib.p2pb_pointwise_wgrad_ws_floats.restype = ctypes.c_size_t
         _lib.p2pb_optim_entry_bytes.restype = ctypes.c_size_t
+        _lib.p2pb_pairwise_chamfer_ws_bytes.restype = ctypes.c_size_t
+        _lib.p2pb_pairwise_emd_ws_bytes.restype = ctypes.c_size_t
+        _lib.p2pb_occupancy_ws_bytes.restype = ctypes.c_size_t
         have = _lib.p2pb_version() if hasattr(_lib, "p2pb_version") else None
         if have != ABI_VERSION:
             bad, _lib = _lib, None
