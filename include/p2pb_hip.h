@@ -30,13 +30,15 @@ extern "C" {
 
 #define P2PB_EINVAL (-22)
 
-/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (9: the set metrics
+/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (10: the GroupNorm finisher is
+ * passed to p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather as fin_* arguments, the three
+ * entry points that armed one for the thread's next launch removed; 9: the set metrics
  * p2pb_pairwise_chamfer / p2pb_pairwise_emd / p2pb_occupancy_* added; 8: p2pb_softmax_attention_* added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
  * p2pb_conv3d_k3_forward_sparse, arithmetic code 3 in p2pb_set_split_terms_thread, p2pb_group_sub_stats*, p2pb_se_gate_*,
  * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
  * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
-#define P2PB_ABI_VERSION 9
+#define P2PB_ABI_VERSION 10
 
 /* library / device info --------------------------------------------------------------------- */
 int p2pb_version(void);            /* == P2PB_ABI_VERSION of the header the library was built from */
@@ -74,19 +76,6 @@ int p2pb_get_deterministic(void);
  * 6 gathered wide f16x3), or -1 if none; *launches (may be NULL) = how many such launches since the last reset.
  * cin < 0 resets the table. Host-side bookkeeping only (under hipGraph capture: recorded at capture time). */
 int p2pb_debug_pointwise_form(int cin, int cout, int npos, unsigned long long *launches);
-
-/* The GroupNorm(+AdaGN) that FOLLOWS a layer, handed to the layer's own launch: arm, then call a statistics-producing pointwise
- * entry point (p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather with stats_part != NULL) from the same
- * thread. scale / shift / chmean (f32[b, cout]; chmean may be NULL) are then filled in stream order exactly as
- * p2pb_gn_affine_params(b, cout, groups, nslots, count_per_channel, stats_part, gamma, beta, style, style_stride, eps, ...)
- * called right after that launch would fill them (same bits): the entry point puts the gn_affine launch behind the producer
- * (the forms that ran it in the producing kernel's last workgroup measured slower and left in round 5). Replaces the reference's separate
- * nn.GroupNorm / AdaGN pass after each 1x1 convolution (models/pvcnn.py:162-205, models/modules.py:341-358).
- * Arming twice without a consuming launch in between is an error (P2PB_EINVAL); p2pb_gn_finisher_armed(): 1 while one waits. */
-int p2pb_gn_finisher_arm(int groups, double count_per_channel, const float *gamma, const float *beta, const float *style,
-                         int style_stride, float eps, float *scale, float *shift, float *chmean);
-int p2pb_gn_finisher_armed(void);
-void p2pb_gn_finisher_disarm(void); /* drop an armed finisher whose producing launch did not happen (error paths) */
 
 /* Voxelization.forward normalisation (models/pvcnn.py:215-228): centre on the mean, divide by
  * 2*max-norm (+eps), +0.5, *r, clamp [0,r-1]; also the half-to-even rounded int voxel coords.
@@ -466,7 +455,20 @@ size_t p2pb_pointwise_stats_floats(int b, int cout, int npos);
 int p2pb_pointwise_conv_forward(int b, int cin, int cout, int npos, const float *in, const void *wp,
                                 const float *bias, const float *bias_b, const float *in_scale,
                                 const float *in_shift, int in_swish, int flags, float *out, float *stats_part,
-                                void *stream);
+                                double fin_count_per_channel, int fin_groups, const float *fin_gamma, const float *fin_beta,
+                                const float *fin_style, int fin_style_stride, float fin_eps, float *fin_scale, float *fin_shift,
+                                float *fin_chmean, void *stream);
+/* fin_*: the GroupNorm(+AdaGN) that FOLLOWS the layer, handed to the layer's own launch (here, p2pb_pointwise_conv_pool_forward and
+ * p2pb_pointwise_conv_pool_gather). fin_scale == NULL: none, the other nine are ignored. Otherwise fin_scale / fin_shift /
+ * fin_chmean (f32[b, cout]; fin_chmean may be NULL) are filled in stream order exactly as
+ * p2pb_gn_affine_params(b, cout, fin_groups, nslots, fin_count_per_channel, stats_part, fin_gamma, fin_beta, fin_style,
+ * fin_style_stride, fin_eps, ...) called right after this launch would fill them (same bits; nslots = ceil(P / 256) * 4 with
+ * P = npos, m * u for the gather form): the entry point puts the gn_affine
+ * launch behind the producer (the forms that ran it in the producing kernel's last workgroup measured slower and left in
+ * round 5). Replaces the reference's separate nn.GroupNorm / AdaGN pass after each 1x1 convolution (models/pvcnn.py:162-205,
+ * models/modules.py:341-358). P2PB_EINVAL, before anything is launched, for stats_part == NULL, fin_shift == NULL,
+ * fin_count_per_channel <= 0 or a shape p2pb_gn_affine_params refuses (cout % fin_groups != 0, cout / fin_groups > 256,
+ * fin_style != NULL with fin_style_stride < 2 * cout). The arguments are all the state there is: nothing is kept between calls. */
 /* flags bit 5: point-major output, out f32[b,npos,cout] (what p2pb_group_sub / p2pb_three_interpolate_add gather
  * whole rows from); stats_part must be NULL.
  * flags bit 2: wp is the split pack below and the GEMM runs in the split-operand form (p2pb_set_split_terms; bf16x6: three bf16 terms per fp32
@@ -490,14 +492,19 @@ size_t p2pb_pointwise_minmax_floats(int b, int cout, int npos, int pool_u, int f
 int p2pb_pointwise_conv_pool_forward(int b, int cin, int cout, int npos, const float *in, const void *wp,
                                      const float *bias, const float *bias_b, const float *in_scale,
                                      const float *in_shift, int in_swish, int flags, float *out, float *stats_part,
-                                     int pool_u, float *minmax, void *stream);
+                                     int pool_u, float *minmax, double fin_count_per_channel, int fin_groups,
+                                     const float *fin_gamma, const float *fin_beta, const float *fin_style, int fin_style_stride,
+                                     float fin_eps, float *fin_scale, float *fin_shift, float *fin_chmean, void *stream);
 /* The same for the grouped tensor of a set abstraction WITHOUT building it: operand[ci, (mi, ui)] = zt[b, idx[b,mi,ui], ci]
  * - cxt[b, mi, ci] gathered on load from the point-major rows zt f32[b,n,cin] / cxt f32[b,m,cin] (or NULL) -- exactly what
  * p2pb_group_sub would have written as f32[b,cin,m*u] (call it with out = NULL for the statistics in_scale / in_shift are
  * folded from). Split pack, f16x3 arithmetic, cin % 8 == 0; minmax f32[b,cout,m,2]; the output itself is never stored. */
 int p2pb_pointwise_conv_pool_gather(int b, int cin, int cout, int n, int m, int u, const float *zt, const float *cxt,
                                     const int *idx, const void *wp_split, const float *bias, const float *in_scale,
-                                    const float *in_shift, int in_swish, float *stats_part, float *minmax, void *stream);
+                                    const float *in_shift, int in_swish, float *stats_part, float *minmax,
+                                    double fin_count_per_channel, int fin_groups, const float *fin_gamma, const float *fin_beta,
+                                    const float *fin_style, int fin_style_stride, float fin_eps, float *fin_scale,
+                                    float *fin_shift, float *fin_chmean, void *stream);
 /* nn.Linear on a handful of rows (the per-evaluation Linears: AdaGN styles models/modules.py:337-345, time embedding
  * models/unet_pvc.py:108-112, the global embedding's per-sample bias models/pvcnn.py:926): out[b,co] = bias[co] + sum_ci
  * w[co,ci] x[b,ci]. x f32[b,cin] with row pitch x_stride (floats), w f32[cout,cin] with row pitch w_stride (a column slice of

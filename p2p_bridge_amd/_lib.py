@@ -30,7 +30,7 @@ SYMBOLS = [
     "p2pb_pointwise_split_packed_bytes", "p2pb_pointwise_pack_weights_split", "p2pb_pointwise_pool_supported", "p2pb_pointwise_minmax_floats", "p2pb_pointwise_conv_pool_forward",
     "p2pb_minmax_act", "p2pb_linear_attention_forward", "p2pb_linear_attention_backward", "p2pb_softmax_attention_forward", "p2pb_softmax_attention_backward",
     "p2pb_approxmatch_temp_floats", "p2pb_approxmatch_forward_ws", "p2pb_pointwise_conv_pool_gather", "p2pb_chamfer_ws_bytes", "p2pb_chamfer_forward_ws", "p2pb_radius_count", "p2pb_radius_fill", "p2pb_merge_accumulate", "p2pb_merge_finish", "p2pb_gn_affine_params_ex", "p2pb_norm_act_backward", "p2pb_norm_act_backward_ex", "p2pb_grouping_backward_pitched", "p2pb_three_nn_interpolate_backward_pitched", "p2pb_affine_act_train", "p2pb_conv3d_k3_wgrad_ws_floats", "p2pb_conv3d_k3_wgrad", "p2pb_conv3d_k3_wgrad_occ_ws_floats", "p2pb_conv3d_k3_wgrad_occ", "p2pb_pointwise_wgrad_ws_floats", "p2pb_pointwise_wgrad",
-    "p2pb_debug_pointwise_form", "p2pb_linear_rows", "p2pb_gn_finisher_arm", "p2pb_gn_finisher_armed", "p2pb_gn_finisher_disarm", "p2pb_fps_grid_ws_bytes", "p2pb_furthest_point_sampling_grid",
+    "p2pb_debug_pointwise_form", "p2pb_linear_rows", "p2pb_fps_grid_ws_bytes", "p2pb_furthest_point_sampling_grid",
     "p2pb_optim_entry_bytes", "p2pb_optim_chunk", "p2pb_optim_clip_adam_step",
     "p2pb_conv3d_k3_pack_weights_split_adjoint", "p2pb_pointwise_pack_weights_adjoint", "p2pb_pointwise_pack_weights_split_adjoint",
     "p2pb_conv3d_k3_pack_weights_split_amax", "p2pb_pointwise_pack_weights_split_amax",
@@ -39,7 +39,7 @@ SYMBOLS = [
     "p2pb_occupancy_grid_cells", "p2pb_occupancy_ws_bytes", "p2pb_occupancy_counts",
 ]
 
-ABI_VERSION = 9  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
+ABI_VERSION = 10  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
 
 _lib = None
 

@@ -127,28 +127,3 @@ int p2pb_zero_async(void *p, size_t nbytes, hipStream_t s) {
   hipLaunchKernelGGL(zero_words_kernel, dim3(grid), dim3(256), 0, s, (unsigned *)p, nwords);
   return (int)hipGetLastError();
 }
-
-// ---- the GroupNorm finisher handed to the NEXT statistics-producing launch of this thread (common.h GnFinish) ----
-// p2pb_gn_finisher_arm stores the descriptor; the producer's launcher takes it (p2pb_gn_finisher_take) and launches
-// gn_affine_kernel right behind the producer, in stream order (pointwise.hip pw_finish_behind).
-namespace {
-thread_local bool tl_fin_armed = false;
-thread_local GnFinish tl_fin;
-}  // namespace
-extern "C" int p2pb_gn_finisher_arm(int groups, double count_per_channel, const float *gamma, const float *beta, const float *style,
-                                    int style_stride, float eps, float *scale, float *shift, float *chmean) {
-  if (groups <= 0 || !scale || !shift || !(count_per_channel > 0.0) || tl_fin_armed) return P2PB_EINVAL;
-  tl_fin.gamma = gamma, tl_fin.beta = beta, tl_fin.style = style, tl_fin.scale = scale, tl_fin.shift = shift, tl_fin.chmean = chmean;
-  tl_fin.count_per_channel = count_per_channel, tl_fin.style_stride = style_stride;
-  tl_fin.groups = groups, tl_fin.eps = eps;
-  tl_fin_armed = true;
-  return 0;
-}
-extern "C" int p2pb_gn_finisher_armed(void) { return tl_fin_armed ? 1 : 0; }
-extern "C" void p2pb_gn_finisher_disarm(void) { tl_fin_armed = false; }  // (a caller whose producing launch never happened)
-bool p2pb_gn_finisher_take(GnFinish *out) {
-  if (!tl_fin_armed) return false;
-  *out = tl_fin;
-  tl_fin_armed = false;
-  return true;
-}

@@ -134,7 +134,7 @@ __device__ __forceinline__ float f16_weight_scale(float wmax) {
 // ---- GroupNorm(+AdaGN) finisher: the {sum, sum of squares} partials of a producing kernel -> per-(sample, channel) scale / shift ----
 // (the arithmetic of gn_affine_kernel, pvconv_finish.hip, which calls this too: one workgroup, >= 256 threads of it, per (sample, group);
 //  fixed summation order, double accumulation: the same bits whichever kernel runs it.) Callers: gn_affine_kernel -- also the launch
-// that pointwise.hip puts behind a producer whose caller armed a finisher (p2pb_gn_finisher_arm) -- and the small kernels that fold
+// that pointwise.hip puts behind a producer whose caller passed a finisher (the fin_* arguments) -- and the small kernels that fold
 // the norm into their own prologue (far_field_kernel, pvconv_tail_kernel, minmax_act_pool_kernel). Round 4's forms that ran it in
 // the LAST workgroup of the producing GEMM (tickets, device-scope partials) measured slower than the launch they replaced
 // (248.5 -> 255-260 ms per sample call) and left the library in round 5.
@@ -406,9 +406,7 @@ enum {
   P2PB_FORM_PW_GATHER = 6,    // pw_wide_kernel<GATHER> (grouped operand built on the fly)
 };
 void p2pb_note_pointwise_form(int cin, int cout, int npos, int form);
-// the GroupNorm finisher armed for this thread's next statistics-producing launch (abi.hip) and the launch that runs it behind
-// the producer (pvconv_finish.hip)
-bool p2pb_gn_finisher_take(GnFinish *out);
+// the launch that runs a GroupNorm finisher behind its producer (pvconv_finish.hip; pointwise.hip pw_finish_behind)
 int p2pb_gn_affine_launch(int b, int c, int nslots, const float *part, const GnFinish &f, hipStream_t s);
 
 // value of `key` in P2PB_EXPERIMENT="key=value;key=value" (the one variable behind every A/B switch: p2p_bridge_amd/_experiment.py), or

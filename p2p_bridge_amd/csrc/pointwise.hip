@@ -1091,20 +1091,24 @@ extern "C" int p2pb_pointwise_pack_weights_split_amax(int cout, int cin, const f
   return amax_bits ? pw_pack_split(cout, cin, w, wp, false, stream, amax_bits) : P2PB_EINVAL;
 }
 
-// the finisher the entry point took for this launch (abi.hip p2pb_gn_finisher_arm); a launcher that hands it to its kernel
-// clears `pending`, otherwise the entry point launches gn_affine_kernel behind the producer
-static thread_local GnFinish tl_pw_fin;
-static thread_local bool tl_pw_fin_pending = false;
-static int pw_finish_behind(int rc, int b, int cout, int P, const float *stats_part, hipStream_t s) {
-  if (!tl_pw_fin_pending) return rc;
-  tl_pw_fin_pending = false;
-  if (rc != 0) return rc;
-  if (!stats_part) return P2PB_EINVAL;  // (a finisher armed for a launch without statistics)
-  // the checks of p2pb_gn_affine_params_ex (a MyGroupNorm(32, cout) with cout % 32 != 0, or cout / groups > 256, ran
-  // gn_finish_group with a truncated group / past its 256-entry LDS table and read gamma out of bounds)
-  const GnFinish &f = tl_pw_fin;
-  if (f.groups <= 0 || cout % f.groups != 0 || cout / f.groups > 256 || (f.style && f.style_stride < 2 * cout)) return P2PB_EINVAL;
-  return p2pb_gn_affine_launch(b, cout, (P + 255) / 256 * 4, stats_part, tl_pw_fin, s);
+// The GroupNorm(+AdaGN) that follows the layer (the fin_* arguments of the three statistics-producing entry points below, common.h
+// GnFinish; scale == NULL: none). An entry point checks it BEFORE launching anything (pw_fin_ok) and puts gn_affine_kernel behind
+// its producer, in stream order (pw_finish_behind).
+static GnFinish pw_fin(double count_per_channel, int groups, const float *gamma, const float *beta, const float *style,
+                       int style_stride, float eps, float *scale, float *shift, float *chmean) {
+  GnFinish f = {};
+  f.gamma = gamma, f.beta = beta, f.style = style, f.scale = scale, f.shift = shift, f.chmean = chmean;
+  f.count_per_channel = count_per_channel, f.style_stride = style_stride, f.groups = groups, f.eps = eps;
+  return f;
+}
+// (gn_shape_ok, ADVICE r4: a MyGroupNorm(32, cout) with cout % 32 != 0, or cout / groups > 256, ran gn_finish_group with a
+//  truncated group / past its 256-entry LDS table and read gamma out of bounds)
+static bool pw_fin_ok(const GnFinish &f, int cout, const float *stats_part) {
+  return !f.scale || (stats_part && f.shift && f.count_per_channel > 0.0 && gn_shape_ok(cout, f.groups, f.style, f.style_stride));
+}
+static int pw_finish_behind(int rc, int b, int cout, int P, const float *stats_part, const GnFinish &f, hipStream_t s) {
+  if (rc != 0 || !f.scale) return rc;
+  return p2pb_gn_affine_launch(b, cout, (P + 255) / 256 * 4, stats_part, f, s);
 }
 
 static int pw_launch_split(int b, int cin, int cout, int P, const float *in, const void *wp, const float *bias,
@@ -1286,11 +1290,16 @@ static int pw_conv_forward_impl(int b, int cin, int cout, int npos, const float 
 extern "C" int p2pb_pointwise_conv_forward(int b, int cin, int cout, int npos, const float *in, const void *wp_any,
                                            const float *bias, const float *bias_b, const float *in_scale,
                                            const float *in_shift, int in_swish, int flags, float *out,
-                                           float *stats_part, void *stream) {
-  tl_pw_fin_pending = p2pb_gn_finisher_take(&tl_pw_fin);  // (a finisher armed for this launch: abi.hip)
+                                           float *stats_part, double fin_count_per_channel, int fin_groups,
+                                           const float *fin_gamma, const float *fin_beta, const float *fin_style,
+                                           int fin_style_stride, float fin_eps, float *fin_scale, float *fin_shift,
+                                           float *fin_chmean, void *stream) {
+  const GnFinish f = pw_fin(fin_count_per_channel, fin_groups, fin_gamma, fin_beta, fin_style, fin_style_stride, fin_eps, fin_scale,
+                            fin_shift, fin_chmean);
+  if (!pw_fin_ok(f, cout, stats_part)) return P2PB_EINVAL;
   const int rc = pw_conv_forward_impl(b, cin, cout, npos, in, wp_any, bias, bias_b, in_scale, in_shift, in_swish, flags, out,
                                       stats_part, stream);
-  return pw_finish_behind(rc, b, cout, npos, stats_part, (hipStream_t)stream);
+  return pw_finish_behind(rc, b, cout, npos, stats_part, f, (hipStream_t)stream);
 }
 
 // pool_u = neighbourhood size (4, 8, 16, 32 or 64 consecutive positions) or 0 for the global pool
@@ -1338,11 +1347,16 @@ extern "C" int p2pb_pointwise_conv_pool_forward(int b, int cin, int cout, int np
                                                 const void *wp_any, const float *bias, const float *bias_b,
                                                 const float *in_scale, const float *in_shift, int in_swish, int flags,
                                                 float *out, float *stats_part, int pool_u, float *minmax,
+                                                double fin_count_per_channel, int fin_groups, const float *fin_gamma,
+                                                const float *fin_beta, const float *fin_style, int fin_style_stride,
+                                                float fin_eps, float *fin_scale, float *fin_shift, float *fin_chmean,
                                                 void *stream) {
-  tl_pw_fin_pending = p2pb_gn_finisher_take(&tl_pw_fin);
+  const GnFinish f = pw_fin(fin_count_per_channel, fin_groups, fin_gamma, fin_beta, fin_style, fin_style_stride, fin_eps, fin_scale,
+                            fin_shift, fin_chmean);
+  if (!pw_fin_ok(f, cout, stats_part)) return P2PB_EINVAL;
   const int rc = pw_conv_pool_forward_impl(b, cin, cout, npos, in, wp_any, bias, bias_b, in_scale, in_shift, in_swish, flags, out,
                                            stats_part, pool_u, minmax, stream);
-  return pw_finish_behind(rc, b, cout, npos, stats_part, (hipStream_t)stream);
+  return pw_finish_behind(rc, b, cout, npos, stats_part, f, (hipStream_t)stream);
 }
 
 // The last layer of a set abstraction's MLP on the GROUPED tensor without building it (pw_wide_kernel<GATHER>):
@@ -1350,14 +1364,19 @@ extern "C" int p2pb_pointwise_conv_pool_forward(int b, int cin, int cout, int np
 //   idx i32[b,m,u]: what p2pb_group_sub writes out as f32[b,cin,m*u]), folded norm + Swish applied on load, then the
 //   1x1 convolution with the statistics + neighbourhood {min, max} epilogue of p2pb_pointwise_conv_pool_forward (output
 //   never stored). wp_split = the split pack; f16x3 arithmetic; cin % 8 == 0, u in {4, 8, 16, 32, 64}.
-static int pw_conv_pool_gather_impl(int b, int cin, int cout, int n, int m, int u, const float *zt,
+extern "C" int p2pb_pointwise_conv_pool_gather(int b, int cin, int cout, int n, int m, int u, const float *zt,
                                                const float *cxt, const int *idx, const void *wp_split, const float *bias,
                                                const float *in_scale, const float *in_shift, int in_swish,
-                                               float *stats_part, float *minmax, void *stream) {
+                                               float *stats_part, float *minmax, double fin_count_per_channel,
+                                               int fin_groups, const float *fin_gamma, const float *fin_beta,
+                                               const float *fin_style, int fin_style_stride, float fin_eps, float *fin_scale,
+                                               float *fin_shift, float *fin_chmean, void *stream) {
+  const GnFinish f = pw_fin(fin_count_per_channel, fin_groups, fin_gamma, fin_beta, fin_style, fin_style_stride, fin_eps, fin_scale,
+                            fin_shift, fin_chmean);
   const long npos = (long)m * u;
   if (b <= 0 || cin <= 0 || cout <= 0 || n <= 0 || m <= 0 || !zt || !idx || !wp_split || !in_scale || !in_shift ||
       !stats_part || !minmax || (cin & 7) || npos > 0x7fffffffL || !p2pb_pointwise_pool_supported((int)npos, u) || u == 0 ||
-      p2pb_g_split_terms != SPLIT_F16X3 || (((uintptr_t)zt | (uintptr_t)cxt) & 15))
+      p2pb_g_split_terms != SPLIT_F16X3 || (((uintptr_t)zt | (uintptr_t)cxt) & 15) || !pw_fin_ok(f, cout, stats_part))
     return P2PB_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int P = (int)npos, nslots = (P + 255) / 256 * 4, gl = pool_lanes(u);
@@ -1377,19 +1396,8 @@ static int pw_conv_pool_gather_impl(int b, int cin, int cout, int n, int m, int 
   }
 #undef LAUNCHG
   p2pb_note_pointwise_form(cin, cout, P, P2PB_FORM_PW_GATHER);
-  return p2pb_launch_status();
+  return pw_finish_behind(p2pb_launch_status(), b, cout, P, stats_part, f, s);
 }
-
-extern "C" int p2pb_pointwise_conv_pool_gather(int b, int cin, int cout, int n, int m, int u, const float *zt,
-                                               const float *cxt, const int *idx, const void *wp_split, const float *bias,
-                                               const float *in_scale, const float *in_shift, int in_swish,
-                                               float *stats_part, float *minmax, void *stream) {
-  tl_pw_fin_pending = p2pb_gn_finisher_take(&tl_pw_fin);
-  const int rc = pw_conv_pool_gather_impl(b, cin, cout, n, m, u, zt, cxt, idx, wp_split, bias, in_scale, in_shift, in_swish,
-                                          stats_part, minmax, stream);
-  return pw_finish_behind(rc, b, cout, (int)((long)m * u), stats_part, (hipStream_t)stream);
-}
-
 
 // y = max(act(scale*min + shift), act(scale*max + shift)):
 //   nslots == 0: minmax f32[b, c, m, 2] -> y f32[b, c, m]      (set-abstraction neighbour max)

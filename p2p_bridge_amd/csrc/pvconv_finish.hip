@@ -40,8 +40,7 @@ extern "C" int p2pb_gn_affine_params_ex(int b, int c, int groups, int nslots, do
                                         const float *part, const float *gamma, const float *beta, const float *style,
                                         int style_stride, float eps, float *scale, float *shift, float *chmean,
                                         float *mean_rstd, void *stream) {
-  if (b <= 0 || c <= 0 || groups <= 0 || c % groups != 0 || nslots <= 0 || c / groups > 256) return P2PB_EINVAL;
-  if (style && style_stride < 2 * c) return P2PB_EINVAL;
+  if (b <= 0 || c <= 0 || nslots <= 0 || !gn_shape_ok(c, groups, style, style_stride)) return P2PB_EINVAL;
   hipLaunchKernelGGL(gn_affine_kernel, dim3(groups, b), dim3(256), 0, (hipStream_t)stream, c, groups, nslots,
                      count_per_channel, part, gamma, beta, style, style_stride, eps, scale, shift, chmean, mean_rstd);
   return p2pb_launch_status();

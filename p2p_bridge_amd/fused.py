@@ -397,11 +397,7 @@ def gn_affine_params(part, count_per_channel, groups, gamma, beta, style=None, e
     scale = torch.empty(b, c, dtype=F32, device=part.device)
     shift = torch.empty_like(scale)
     chmean = torch.empty_like(scale) if want_mean else None
-    stride = 0
-    if style is not None:
-        if style.stride(1) != 1 or style.shape[1] != 2 * c:
-            style = style.contiguous()
-        stride = style.stride(0)
+    style, stride = _style_arg(style, c)
     call("p2pb_gn_affine_params", _i(b), _i(c), _i(groups), _i(nslots), _d(float(count_per_channel)), ptr(part),
          ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps), ptr(scale), ptr(shift), ptr(chmean), stream_ptr())
     return scale, shift, chmean
@@ -553,23 +549,20 @@ def use_split_pw(ci: int, co: int, npos: int, math=None) -> bool:
             and npos % 4 == 0)
 
 
-def arm_finisher(fin, b, c, device):
-    """hand the GroupNorm that follows a layer to the layer's own launch (csrc/common.h GnFinish): fin = (count_per_channel,
-    groups, gamma, beta, style | None, eps, want_mean) -> (scale, shift, chmean | None) f32[B,C], filled in stream order by the
-    NEXT statistics-producing launch of this thread: its entry point puts the gn_affine launch right behind the producer (one
-    Python call and one ctypes call fewer per layer; the values and bits of a separate gn_affine_params call)"""
+def _fin_args(fin, b, c, device):
+    """the GroupNorm that follows a layer, handed to the layer's own launch (csrc/common.h GnFinish): fin = (count_per_channel,
+    groups, gamma, beta, style | None, eps, want_mean) | None -> ((scale, shift, chmean | None) f32[B,C] | None, the ten fin_*
+    arguments of the statistics-producing pointwise entry points, the style tensor they point into). The entry point puts the
+    gn_affine launch right behind the producer: the values and bits of a separate gn_affine_params call, filled in stream order"""
+    if fin is None:
+        return None, (_d(0.0), _i(0), ptr(None), ptr(None), ptr(None), _i(0), _f(0.0), ptr(None), ptr(None), ptr(None)), None
     count, groups, gamma, beta, style, eps, want_mean = fin
     scale = torch.empty(b, c, dtype=F32, device=device)
     shift = torch.empty_like(scale)
     chmean = torch.empty_like(scale) if want_mean else None
-    stride = 0
-    if style is not None:
-        if style.stride(1) != 1 or style.shape[1] != 2 * c:
-            style = style.contiguous()
-        stride = style.stride(0)
-    call("p2pb_gn_finisher_arm", _i(int(groups)), _d(float(count)), ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps),
-         ptr(scale), ptr(shift), ptr(chmean))
-    return (scale, shift, chmean), style  # (style: kept alive by the caller until the launch is enqueued)
+    style, stride = _style_arg(style, c)
+    return (scale, shift, chmean), (_d(float(count)), _i(int(groups)), ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps),
+                                    ptr(scale), ptr(shift), ptr(chmean)), style
 
 
 @_honours_pin(1)
@@ -607,28 +600,23 @@ def pw_conv(x, conv, in_scale=None, in_shift=None, swish=False, stats=True, bias
         nfl = lib().p2pb_pointwise_stats_floats(_i(b), _i(co), _i(p))
         st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
     bias = conv.bias if use_bias else None
-    aff = keep = None
-    if fin is not None:  # fin: the norm that follows (arm_finisher) -> the result carries (scale, shift, chmean) as well
-        assert st is not None
-        aff, keep = arm_finisher(fin, b, co, x.device)
-    try:
-        if pool_u is None:
-            call("p2pb_pointwise_conv_forward", _i(b), _i(ci), _i(co), _i(p), ptr(x), ptr(wp), ptr(bias), ptr(bias_b),
-                 ptr(in_scale), ptr(in_shift), _i(int(swish)), flags, ptr(y), ptr(st), stream_ptr())
-            return (y, st) if fin is None else (y, st, aff)
-        return _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, pool_u, b, ci, co, p, fin, aff)
-    finally:
-        if fin is not None:
-            lib().p2pb_gn_finisher_disarm()  # (no-op after a launch that took it; an error path must not leave it armed)
+    # fin: the norm that follows -> the result carries (scale, shift, chmean) as well; style_kept: alive until the call returns
+    aff, fin_args, style_kept = _fin_args(fin, b, co, x.device)
+    if pool_u is not None:
+        return _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, pool_u, b, ci, co, p, aff, fin_args)
+    call("p2pb_pointwise_conv_forward", _i(b), _i(ci), _i(co), _i(p), ptr(x), ptr(wp), ptr(bias), ptr(bias_b),
+         ptr(in_scale), ptr(in_shift), _i(int(swish)), flags, ptr(y), ptr(st), *fin_args, stream_ptr())
+    return (y, st) if fin is None else (y, st, aff)
 
 
-def _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, pool_u, b, ci, co, p, fin, aff):
+def _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, pool_u, b, ci, co, p, aff, fin_args):
     nmm = lib().p2pb_pointwise_minmax_floats(_i(b), _i(co), _i(p), _i(pool_u), flags)
     mm = torch.empty((b, nmm // (b * co * 2), co, 2) if pool_u == 0 else (b, co, p // pool_u, 2), dtype=F32,
                      device=x.device)
     call("p2pb_pointwise_conv_pool_forward", _i(b), _i(ci), _i(co), _i(p), ptr(x), ptr(wp), ptr(bias), ptr(bias_b),
-         ptr(in_scale), ptr(in_shift), _i(int(swish)), flags, ptr(y), ptr(st), _i(pool_u), ptr(mm), stream_ptr())
-    return (y, st, mm) if fin is None else (y, st, mm, aff)
+         ptr(in_scale), ptr(in_shift), _i(int(swish)), flags, ptr(y), ptr(st), _i(pool_u), ptr(mm), *fin_args,
+         stream_ptr())
+    return (y, st, mm) if aff is None else (y, st, mm, aff)
 
 
 def linear_rows(x, weight, bias=None):
@@ -687,15 +675,9 @@ def pw_conv_pool_gather(zt, cxt, idx, conv, in_scale, in_shift, swish=True, fin=
     nfl = lib().p2pb_pointwise_stats_floats(_i(b), _i(co), _i(p))
     st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=zt.device)
     mm = torch.empty(b, co, m, 2, dtype=F32, device=zt.device)
-    aff = keep = None
-    if fin is not None:
-        aff, keep = arm_finisher(fin, b, co, zt.device)
-    try:
-        call("p2pb_pointwise_conv_pool_gather", _i(b), _i(ci), _i(co), _i(n), _i(m), _i(u), ptr(zt), ptr(cxt), ptr(idx), ptr(wp),
-             ptr(conv.bias), ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(st), ptr(mm), stream_ptr())
-    finally:
-        if fin is not None:
-            lib().p2pb_gn_finisher_disarm()
+    aff, fin_args, style_kept = _fin_args(fin, b, co, zt.device)  # (style_kept: alive until the call returns)
+    call("p2pb_pointwise_conv_pool_gather", _i(b), _i(ci), _i(co), _i(n), _i(m), _i(u), ptr(zt), ptr(cxt), ptr(idx), ptr(wp),
+         ptr(conv.bias), ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(st), ptr(mm), *fin_args, stream_ptr())
     return (st, mm) if fin is None else (st, mm, aff)
 
 

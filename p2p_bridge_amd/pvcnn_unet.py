@@ -382,24 +382,9 @@ def _group_norm_of(norm):
     return norm.norm if isinstance(norm, AdaGN) else (norm.group_norm if isinstance(norm, MyGroupNorm) else norm)
 
 
-def norm_affine(norm, part, count, cond, want_mean=False):
-    """AdaGN / GroupNorm / MyGroupNorm folded to per-(sample, channel) (scale, shift[, channel mean]) from the
-    producing kernel's statistics: {sum, sumsq} partials -> arrays through fused.gn_affine_params (one launch)"""
-    from . import fused
-
-    style = None
-    if isinstance(norm, AdaGN):
-        if cond is None:
-            raise RuntimeError("AdaGN needs the global embedding")
-        style = cond.style(norm) if isinstance(cond, _Styles) else norm.emd(cond)
-    gn = _group_norm_of(norm)
-    out = fused.gn_affine_params(part, count, gn.num_groups, gn.weight, gn.bias, style, gn.eps, want_mean)
-    return out if want_mean else out[:2]
-
-
 def norm_fin(norm, count, cond, want_mean=False):
-    """the same norm as a finisher descriptor for the PRODUCING launch (fused.pw_conv(..., fin=...): csrc/common.h GnFinish): the
-    scale / shift arrays come back with the producer's outputs, no gn_affine launch between producer and consumer"""
+    """AdaGN / GroupNorm / MyGroupNorm as a finisher descriptor for the PRODUCING launch (fused.pw_conv(..., fin=...): csrc/common.h
+    GnFinish): the scale / shift arrays come back with the producer's outputs, no gn_affine launch between producer and consumer"""
     style = None
     if isinstance(norm, AdaGN):
         if cond is None:
@@ -407,6 +392,15 @@ def norm_fin(norm, count, cond, want_mean=False):
         style = cond.style(norm) if isinstance(cond, _Styles) else norm.emd(cond)
     gn = _group_norm_of(norm)
     return (count, gn.num_groups, gn.weight, gn.bias, style, gn.eps, want_mean)
+
+
+def norm_affine(norm, part, count, cond, want_mean=False):
+    """the same norm folded to per-(sample, channel) (scale, shift[, channel mean]) from the producing kernel's statistics:
+    {sum, sumsq} partials -> arrays through fused.gn_affine_params (one launch)"""
+    from . import fused
+
+    out = fused.gn_affine_params(part, *norm_fin(norm, count, cond, want_mean))
+    return out if want_mean else out[:2]
 
 
 class SharedMLP(nn.Module):

@@ -24,6 +24,7 @@ def test_degenerate_sizes_are_einval(L):
     x = torch.zeros(64, device="cuda")
     p = L.ptr(x)
     s = L.stream_ptr()
+    no_fin = (ctypes.c_double(0.0), _i(0), NULL, NULL, NULL, _i(0), _f(0.0), NULL, NULL, NULL)  # fin_scale == NULL: no finisher
     calls = {
         "p2pb_furthest_point_sampling": (_i(0), _i(8), _i(2), p, NULL, p, s),
         "p2pb_furthest_point_sampling_grid": (_i(1), _i(8), _i(2), p, NULL, p, s),          # no workspace
@@ -32,7 +33,7 @@ def test_degenerate_sizes_are_einval(L):
         "p2pb_chamfer_forward": (_i(0), _i(4), _i(4), p, p, p, p, p, p, s),
         "p2pb_conv3d_k3_forward": (_i(1), _i(0), _i(8), _i(8), p, p, p, NULL, NULL, _i(0), p, NULL, s),
         "p2pb_conv3d_k3_forward_ex": (_i(1), _i(8), _i(8), _i(5), p, p, p, NULL, NULL, NULL, _i(0), NULL, _i(4), p, NULL, s),  # r = 5
-        "p2pb_pointwise_conv_forward": (_i(1), _i(8), _i(8), _i(0), p, p, p, NULL, NULL, NULL, _i(0), _i(0), p, NULL, s),
+        "p2pb_pointwise_conv_forward": (_i(1), _i(8), _i(8), _i(0), p, p, p, NULL, NULL, NULL, _i(0), _i(0), p, NULL, *no_fin, s),
         "p2pb_gn_affine_params": (_i(1), _i(12), _i(5), _i(1), ctypes.c_double(4.0), p, NULL, NULL, NULL, _i(0), _f(1e-5), p, p, NULL, s),  # 12 % 5
         "p2pb_radius_count": (_i(1), _i(4), p, p, _f(-1.0), p, s),                             # negative radius
         "p2pb_linear_attention_forward": (_i(1), _i(2), _i(16), _i(8), p, p, NULL, s),        # dim_head != 32
@@ -50,6 +51,12 @@ def test_degenerate_sizes_are_einval(L):
     for bad in (dict(drop=1.0, seed=p), dict(drop=0.2), dict(gmean=p, swish=1), dict(gmean=p, drop=0.1, seed=p), dict(pitch=63),
                 dict(pitch=66), dict(dres=p, drgate=p), dict(res=p, rgate=p, dres=p)):
         assert lib.p2pb_norm_act_backward_ex(*nab(**bad)) == -22, bad
+    # the GroupNorm finisher of the pointwise entry points is checked before the producer is launched (b, cin, cout, npos; stats;
+    # groups; style, stride): no statistics to finish, 12 % 5, a style row shorter than 2 * cout
+    pwf = lambda co, st, groups, style, stride: (_i(1), _i(8), _i(co), _i(4), p, p, p, NULL, NULL, NULL, _i(0), _i(0), p, st,  # noqa: E731
+                                                 ctypes.c_double(4.0), _i(groups), NULL, NULL, style, _i(stride), _f(1e-5), p, p, NULL, s)
+    for k, bad in enumerate(((8, NULL, 4, NULL, 0), (12, p, 5, NULL, 0), (8, p, 4, p, 15))):
+        assert lib.p2pb_pointwise_conv_forward(*pwf(*bad)) == -22, k
     for name, args in calls.items():
         rc = getattr(lib, name)(*args)
         assert rc == -22, (name, rc)

@@ -139,7 +139,7 @@ def test_every_op_of_an_evaluation_beside_matrix_kernels_is_bitwise_stable():
     mods = {"fused": fused, "ext": ext}
     not_ops = {"conv_math", "set_conv_math", "use_split", "use_split_pw", "use_wide_f16", "pool_supported", "gather_pool_supported",
                "conv_pre_plan", "enabled", "pack_conv3d_weight", "pack_pointwise_weight", "lib", "call", "check", "ptr", "stream_ptr",
-               "fps_coop_fallbacks", "arm_finisher"}
+               "fps_coop_fallbacks"}
     names = [(mname, k) for mname, m in mods.items() for k, v in vars(m).items()
              if isinstance(v, types.FunctionType) and v.__module__ == m.__name__ and not k.startswith("_") and k not in not_ops]
     ca = _record_evaluation(net, mods, names, x[:16].contiguous(), t)

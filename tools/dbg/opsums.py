@@ -21,7 +21,7 @@ x = x.cuda()
 t = torch.full((B,), 500.0, device="cuda")
 mods = {"fused": fused, "ext": ext}
 skip = {"conv_math", "set_conv_math", "use_split", "use_split_pw", "use_wide_f16", "pool_supported", "gather_pool_supported", "conv_pre_plan",
-        "enabled", "pack_conv3d_weight", "pack_pointwise_weight", "lib", "call", "check", "ptr", "stream_ptr", "fps_coop_fallbacks", "arm_finisher"}
+        "enabled", "pack_conv3d_weight", "pack_pointwise_weight", "lib", "call", "check", "ptr", "stream_ptr", "fps_coop_fallbacks"}
 depth = [0]
 n = [0]
 
