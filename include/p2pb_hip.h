@@ -452,6 +452,16 @@ int p2pb_pointwise_pack_weights(int cout, int cin, const float *w /* [cout][cin]
 size_t p2pb_pointwise_stats_floats(int b, int cout, int npos);
 /* out[b,cout,npos] = bias[cout] (+ bias_b[b,cout]) + W * xf(in[b,cin,npos]); xf / stats_part as in
  * p2pb_conv3d_k3_forward (stats_part f32[b, ceil(npos/256)*4, cout, 2]). bias, bias_b may be NULL. */
+/* `flags` of p2pb_pointwise_conv_forward, p2pb_pointwise_conv_pool_forward and p2pb_pointwise_minmax_floats:
+ * bit 2 (4): wp is the split pack (p2pb_pointwise_pack_weights_split, made for the arithmetic of p2pb_set_split_terms) and the GEMM
+ *   runs in the split-operand form (bf16x6: three bf16 terms per fp32 operand, six MFMA products, fp32 accumulate -- see the conv3d
+ *   split pack); needs npos % 4 == 0 and 16-byte aligned in/out. Meant for the matrix-bound layers (wide channel counts).
+ * bit 5 (32), p2pb_pointwise_conv_forward only: point-major output, out f32[b,npos,cout] (what p2pb_group_sub /
+ *   p2pb_three_interpolate_add gather whole rows from); stats_part must be NULL; needs npos % 4 == 0 and 16-byte aligned in/out.
+ * bit 7 (128, with bit 2, f16x3 arithmetic, 16-byte rows): a NARROW layer (cin or cout < 128) on the split pack -- the
+ *   register-tiled kernel of the fp32 pack with its products on the 16-bit matrix pipe (three MFMAs of K = 16 instead of eight
+ *   exact-fp32 ones of K = 2 per 32x32x16 block); outputs, statistics and minmax in the layout of the fp32-pack form.
+ * The thread arithmetic bf16x3 (p2pb_set_split_terms_thread(3)) runs bit 2 alone: no in_scale, no bit 5, no pooling. */
 int p2pb_pointwise_conv_forward(int b, int cin, int cout, int npos, const float *in, const void *wp,
                                 const float *bias, const float *bias_b, const float *in_scale,
                                 const float *in_shift, int in_swish, int flags, float *out, float *stats_part,
@@ -469,17 +479,8 @@ int p2pb_pointwise_conv_forward(int b, int cin, int cout, int npos, const float 
  * models/modules.py:341-358). P2PB_EINVAL, before anything is launched, for stats_part == NULL, fin_shift == NULL,
  * fin_count_per_channel <= 0 or a shape p2pb_gn_affine_params refuses (cout % fin_groups != 0, cout / fin_groups > 256,
  * fin_style != NULL with fin_style_stride < 2 * cout). The arguments are all the state there is: nothing is kept between calls. */
-/* flags bit 5: point-major output, out f32[b,npos,cout] (what p2pb_group_sub / p2pb_three_interpolate_add gather
- * whole rows from); stats_part must be NULL.
- * flags bit 2: wp is the split pack below and the GEMM runs in the split-operand form (p2pb_set_split_terms; bf16x6: three bf16 terms per fp32
- * operand, six MFMA products, fp32 accumulate -- see the conv3d split pack); needs npos % 4 == 0 and
- * 16-byte aligned in/out. Meant for the matrix-bound layers (wide channel counts). */
 size_t p2pb_pointwise_split_packed_bytes(int cout, int cin);
 int p2pb_pointwise_pack_weights_split(int cout, int cin, const float *w /* [cout][cin] */, void *wp, void *stream);
-/* flags bit 7 (with bit 2, f16x3 arithmetic, 16-byte rows, no in_fold / out_acc): a NARROW layer (cin or cout < 128) on
- * the split pack -- the register-tiled kernel of the fp32 pack with its products on the 16-bit matrix pipe (three MFMAs of
- * K = 16 instead of eight exact-fp32 ones of K = 2 per 32x32x16 block); outputs, statistics and minmax in the layout of the
- * fp32-pack form (p2pb_pointwise_minmax_floats takes the same flags). */
 /* The same GEMM with the max-pool that follows the layer (set abstraction: max over the pool_u = 4..64
  * neighbours, models/pvcnn.py:414; Pnet2Stage: pool_u = 0, max over all positions, :923,930) prepared in the
  * epilogue: minmax receives {min, max} of the raw output per pooling group (pool_u > 0: f32[b,cout,npos/pool_u,2];

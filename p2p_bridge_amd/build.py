@@ -25,7 +25,8 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
          "-Wall", "-Wno-unused-function"]
 
 # the long compiles (minutes each), started first so that the short ones fill in around them
-SLOW = ("conv3d.hip", "conv3d_bf16x6.hip", "conv3d_fp32.hip", "pointwise.hip", "conv3d_bf16x3.hip")
+SLOW = ("conv3d.hip", "conv3d_bf16x6.hip", "conv3d_fp32.hip", "pointwise_split.hip", "conv3d_bf16x3.hip", "pointwise_f16.hip",
+        "pointwise_fp32.hip")
 
 
 def _newer(a, bs):

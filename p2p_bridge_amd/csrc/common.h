@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/p2pb_hip.h"
 
@@ -13,6 +14,19 @@ int p2pb_split_terms_now();  // the calling thread's override, else the process 
 #define p2pb_g_split_terms (p2pb_split_terms_now())
 
 static inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+// a run-time value as a template argument of a launcher: f(std::integral_constant<int, V>) for the V among Vs that equals v
+// (none: P2PB_EINVAL), f(std::true_type / std::false_type) for a flag
+template <int... Vs, class F>
+static inline int for_value(int v, F &&f) {
+  int rc = P2PB_EINVAL;
+  (void)((v == Vs && (rc = f(std::integral_constant<int, Vs>{}), true)) || ...);
+  return rc;
+}
+template <class F>
+static inline int for_flag(bool v, F &&f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // Squared distance with the arithmetic contract of DESIGN.md: nvcc contracts
 // dx*dx + dy*dy + dz*dz into  fma(dz,dz, fma(dy,dy, dx*dx)); the sources are compiled with

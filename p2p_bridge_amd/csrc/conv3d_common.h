@@ -28,7 +28,6 @@
 // skipped. Compact 4x8x8 bricks (instead of full-row bricks) make the zero test fine-grained in 3-D.
 #pragma once
 #include "common.h"
-#include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -121,19 +120,6 @@ struct ConvArgs {
   bool cl, pre;  // voxel-major tensors; `in` is pre-split
   hipStream_t s;
 };
-
-// a run-time value as a template argument of the launchers: f(std::integral_constant<int, R>) for the R among Rs that equals r
-// (none: P2PB_EINVAL), f(std::true_type / std::false_type) for a flag
-template <int... Rs, class F>
-static inline int conv_for_r(int r, F &&f) {
-  int rc = P2PB_EINVAL;
-  (void)((r == Rs && (rc = f(std::integral_constant<int, Rs>{}), true)) || ...);
-  return rc;
-}
-template <class F>
-static inline int conv_for_flag(bool v, F &&f) {
-  return v ? f(std::true_type{}) : f(std::false_type{});
-}
 
 // launchers of the kernels that live in other objects than the entry points of conv3d.hip
 // conv3d_fp32.hip: r in {4, 8, 16, 32} (else P2PB_EINVAL), compact bricks for r >= 16 only, mt = 32-channel tiles per workgroup

@@ -413,9 +413,9 @@ static int conv_compact_go(const ConvArgs &a) {
 }
 template <int TERMS>
 static int conv_compact_launch(int r, const ConvArgs &a) {
-  return conv_for_r<32, 16, 8>(r, [&](auto R) {
+  return for_value<32, 16, 8>(r, [&](auto R) {
     // cout <= 32: one M-tile per workgroup, tiles dealt to four wave columns
-    return conv_for_flag(a.cout <= 32, [&](auto WM1) {
+    return for_flag(a.cout <= 32, [&](auto WM1) {
       constexpr int RR = decltype(R)::value, WM = decltype(WM1)::value ? 1 : 2;
       if constexpr (TERMS == SPLIT_F16X3) {
         if (a.pre) return conv_compact_go<RR, WM, false, TERMS, true>(a);

@@ -326,9 +326,9 @@ static int conv_fp32_go(const ConvArgs &a) {
 }
 template <int R, bool COMPACT>
 static int conv_fp32_form(int mt, const ConvArgs &a) {
-  return conv_for_flag(mt == 2, [&](auto WIDE) {
-    return conv_for_flag(a.in_scale != nullptr, [&](auto XF) {
-      return conv_for_flag(a.cl, [&](auto CL) {
+  return for_flag(mt == 2, [&](auto WIDE) {
+    return for_flag(a.in_scale != nullptr, [&](auto XF) {
+      return for_flag(a.cl, [&](auto CL) {
         return conv_fp32_go<R, COMPACT, decltype(WIDE)::value ? 2 : 1, decltype(XF)::value, decltype(CL)::value>(a);
       });
     });

@@ -262,8 +262,8 @@ __global__ __launch_bounds__(256) void conv3d_fill_kernel(int cout, const float 
 }
 
 void conv3d_fill_launch(int r, const ConvArgs &a, const int *inactive_list, const int *inactive_count, bool stats_only) {
-  conv_for_r<32, 16>(r, [&](auto R) {
-    return conv_for_flag(a.cl, [&](auto CL) {
+  for_value<32, 16>(r, [&](auto R) {
+    return for_flag(a.cl, [&](auto CL) {
       hipLaunchKernelGGL((conv3d_fill_kernel<decltype(R)::value, decltype(CL)::value>), dim3(conv_bricks(r) * a.b), dim3(256), 0, a.s,
                          a.cout, a.bias, a.out_class, inactive_list, inactive_count, stats_only ? (float *)nullptr : a.out,
                          a.stats_part);

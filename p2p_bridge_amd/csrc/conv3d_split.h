@@ -612,15 +612,15 @@ static int conv_split_form(const ConvArgs &a) {
     if (a.in_scale != nullptr || a.cl) return P2PB_EINVAL;
     return conv_split_go<R, MT, false, false, TERMS, false>(a);
   } else {
-    return conv_for_flag(a.in_scale != nullptr, [&](auto XF) {
-      return conv_for_flag(a.cl, [&](auto CL) { return conv_split_go<R, MT, decltype(XF)::value, decltype(CL)::value, TERMS, false>(a); });
+    return for_flag(a.in_scale != nullptr, [&](auto XF) {
+      return for_flag(a.cl, [&](auto CL) { return conv_split_go<R, MT, decltype(XF)::value, decltype(CL)::value, TERMS, false>(a); });
     });
   }
 }
 // r in {4, 8, 16, 32} (else P2PB_EINVAL), mt = 32-channel tiles (= wave rows) per workgroup, 1 or 2
 template <int TERMS>
 static int conv_split_launch(int r, int mt, const ConvArgs &a) {
-  return conv_for_r<32, 16, 8, 4>(r, [&](auto R) {
+  return for_value<32, 16, 8, 4>(r, [&](auto R) {
     return mt == 2 ? conv_split_form<decltype(R)::value, 2, TERMS>(a) : conv_split_form<decltype(R)::value, 1, TERMS>(a);
   });
 }

@@ -1,6 +1,6 @@
 // pw_pp512.h -- the wide 1x1-convolution GEMM of the f16x3 arithmetic (>= 512 output channels in whole 512-blocks, an even
 // number of 32-channel stages), round 4: the ping-pong kernel of round 3 (256 x 256 tile: git history, csrc/pw_pingpong.h) re-tiled to 512 channels x 128 positions.
-// Included by pointwise.hip.
+// Instantiated and launched by pointwise_split.hip.
 //
 // Why (round-3 evidence, profiles/r03f_pmc_pw_pingpong_*, r03b_pingpong_timeline.txt, r03d_pw_presplit_ab.txt): on the
 // 256-channel x 256-position tile a wave's STAGING -- folded norm + Swish (exp, rcp), the fp16-pair split and the LDS write of
@@ -31,6 +31,7 @@
 // positions in its even slot, zero in the odd one; slots past the last tile zeroed by the last tile), {min, max} per slot
 // for the global pooling (pool_u == 0), optional channel-major stores.
 #pragma once
+#include "pw_common.h"
 
 #ifdef PP_TIMELINE  // experiment builds (tools/exp_p5_timeline.py): s_memtime stamps of waves 0 and 4, stored at the very end
 __device__ unsigned long long *pp_tl_buf;

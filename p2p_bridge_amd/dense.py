@@ -4,7 +4,7 @@ embed_feats / classifier / LinearAttention, models/pvcnn.py:162-205,803-823, une
 modules.py:173-174) as autograd Functions. The reference gets these from cuDNN / cuBLAS (TF32); round 1 of this build
 left them on torch / MIOpen in training.
 
-    forward   the inference kernels (csrc/conv3d.hip split-operand implicit GEMM, csrc/pointwise.hip GEMMs), plain mode
+    forward   the inference kernels (csrc/conv3d.hip split-operand implicit GEMM, csrc/pointwise*.hip GEMMs), plain mode
     dX        the SAME forward kernels on dY with a transformed weight: taps flipped + channel roles swapped for the
               convolution (a correlation's adjoint is the correlation with the point-reflected kernel), W^T for 1x1
     dW, db    csrc/wgrad.hip: split-K exact-fp32 MFMA GEMMs over the voxel / position index, deterministic reduction

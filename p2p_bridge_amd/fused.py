@@ -479,7 +479,7 @@ def voxelize_cl(features, vox, r):
     return out, cnt
 
 
-# ------------------------------------------------------------------ shared point MLPs (csrc/pointwise.hip)
+# ------------------------------------------------------------------ shared point MLPs (csrc/pointwise*.hip)
 
 
 def enabled(module: torch.nn.Module, x: torch.Tensor) -> bool:
@@ -537,13 +537,13 @@ PW_SPLIT_MIN_CIN, PW_SPLIT_MIN_COUT = 128, 128  # measured crossover (tools/exp_
 
 
 def use_wide_f16(ci: int, co: int) -> bool:
-    """narrow 1x1 layers on the 16-bit matrix pipe too (csrc/pointwise.hip pw_wide_kernel<TERMS = f16x3>): from
+    """narrow 1x1 layers on the 16-bit matrix pipe too (csrc/pw_wide.h pw_wide_kernel<TERMS = f16x3>, built in pointwise_f16.hip): from
     P2PB_EXPERIMENT wide_f16_min_cin input channels up (default 16: below that a 16-channel step is mostly padding)"""
     return ci >= _experiment.get_int("wide_f16_min_cin", 16)
 
 
 def use_split_pw(ci: int, co: int, npos: int, math=None) -> bool:
-    """the split-operand GEMM (csrc/pointwise.hip pw_split_kernel) for the matrix-bound layers; narrow layers are
+    """the split-operand GEMM (csrc/pw_split.h pw_split_kernel, built in pointwise_split.hip) for the matrix-bound layers; narrow layers are
     HBM-bound and stay on the streaming fp32 kernel"""
     return ((math or conv_math()) in SPLIT_MATHS and ci >= PW_SPLIT_MIN_CIN and co >= PW_SPLIT_MIN_COUT
             and npos % 4 == 0)
@@ -621,7 +621,7 @@ def _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, 
 
 def linear_rows(x, weight, bias=None):
     """nn.Linear on a few rows without BLAS: x f32[B,Cin] (rows may be strided), weight f32[Cout,Cin] (may be a column slice of
-    a wider matrix), bias f32[Cout] | None -> f32[B,Cout]. csrc/pointwise.hip linear_rows_kernel: no scratch memory, so two
+    a wider matrix), bias f32[Cout] | None -> f32[B,Cout]. csrc/pointwise_act.hip linear_rows_kernel: no scratch memory, so two
     sampler chains can replay graphs holding it side by side (a torch matmul bakes a per-stream BLAS workspace into the graph)"""
     if x.stride(-1) != 1 or x.data_ptr() % 16 or x.stride(0) % 4:
         x = x.contiguous()

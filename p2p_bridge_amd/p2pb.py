@@ -411,7 +411,7 @@ class P2PB(nn.Module):
     def _sampler_chains(self, xt) -> int:
         """how many independent sub-batches the graph sampler runs side by side (`self.sample_chains` / P2PB_SAMPLE_CHAINS;
         default "auto": TWO chains for an even batch of >= 16 clouds of <= 16384 points or >= 32 larger clouds, one otherwise).
-        A chain evaluates HALF the batch, and the GEMM dispatch is keyed on the batch a launch sees (csrc/pointwise.hip: the
+        A chain evaluates HALF the batch, and the GEMM dispatch is keyed on the batch a launch sees (csrc/pointwise.hip pw_run_split: the
         256-channel / ping-pong forms need >= 1024 workgroups), so a two-chain run is the same arithmetic per sample only up to
         the kernel form -- results agree with the one-chain run to fp32 rounding (1e-6 level), not bit for bit
         (tests/test_full_size_parity_gpu.py::test_c2_bench_dispatch_*: both against the oracle). Each chain owns a captured

@@ -19,6 +19,59 @@ def L():
     return _lib
 
 
+def _pointwise_refusals(p, q, s):
+    """one row per P2PB_EINVAL condition of the pointwise entry points (csrc/pointwise.hip, pointwise_act.hip): (entry point,
+    arithmetic of the calling thread, arguments). Every row is otherwise well-formed -- b = 1, 8 -> 8 channels (8 -> 16 for the gather
+    form), 8 positions, p a 16-byte aligned buffer -- so the one condition it names is what refuses it; q = p + 4 bytes."""
+    F16, BF6, BF3 = 16, 6, 3
+    d = ctypes.c_double
+    no_fin = (d(0.0), _i(0), NULL, NULL, NULL, _i(0), _f(0.0), NULL, NULL, NULL)
+    bad_fin = (d(4.0), _i(5), NULL, NULL, NULL, _i(0), _f(1e-5), p, p, NULL)  # 16 % 5 != 0: gn_shape_ok refuses
+
+    def conv(npos=8, x=p, xf=NULL, flags=0, out=p, st=NULL):
+        return (_i(1), _i(8), _i(8), _i(npos), x, p, p, NULL, xf, xf, _i(0), _i(flags), out, st, *no_fin, s)
+
+    def pool(npos=8, x=p, flags=0, st=p, u=4, mm=p):
+        return (_i(1), _i(8), _i(8), _i(npos), x, p, p, NULL, NULL, NULL, _i(0), _i(flags), p, st, _i(u), mm, *no_fin, s)
+
+    def gather(cin=8, u=4, zt=p, idx=p, xf=p, fin=no_fin):
+        return (_i(1), _i(cin), _i(16), _i(16), _i(4), _i(u), zt, p, idx, p, p, xf, xf, _i(0), p, p, *fin, s)
+
+    def pool_gn(c=8, groups=4, scale=p):
+        return (_i(1), _i(c), _i(4), p, p, _i(4), d(4.0), _i(groups), NULL, NULL, NULL, _i(0), _f(1e-5), _i(1), scale, p, p, s)
+
+    cf, cp, cg, mg = ("p2pb_pointwise_conv_forward", "p2pb_pointwise_conv_pool_forward", "p2pb_pointwise_conv_pool_gather",
+                      "p2pb_minmax_act_pool_gn")
+    return [
+        (cf, F16, conv(out=NULL)),
+        (cf, F16, conv(flags=32, st=p)),            # point-major output has no statistics
+        (cf, F16, conv(flags=4, npos=6)),           # the split pack needs rows of whole quads ...
+        (cf, F16, conv(flags=4, x=q)),              # ... that start on 16-byte boundaries
+        (cf, F16, conv(flags=4 | 128, npos=6)),
+        (cf, BF6, conv(flags=4 | 128)),             # the wide tiling on the split pack exists in f16x3 only
+        (cf, F16, conv(flags=32, npos=6)),          # fp32 pack: the unaligned fallback has no point-major form
+        (cf, BF3, conv(flags=4, xf=p)),             # bf16x3: plain operand ...
+        (cf, BF3, conv(flags=4 | 32)),              # ... and channel-major output only
+        (cp, F16, pool(mm=NULL)),
+        (cp, F16, pool(st=NULL)),
+        (cp, F16, pool(u=5)),
+        (cp, F16, pool(npos=12, u=8)),              # npos % pool_u
+        (cp, F16, pool(npos=6, u=0)),               # npos % 4
+        (cp, F16, pool(x=q)),
+        (cp, BF3, pool(flags=4)),                   # bf16x3 has no pooling epilogue
+        (cg, F16, gather(cin=12)),                  # cin % 8
+        (cg, F16, gather(u=0)),
+        (cg, F16, gather(idx=NULL)),
+        (cg, F16, gather(xf=NULL)),
+        (cg, F16, gather(zt=q)),
+        (cg, BF6, gather()),                        # the gathered form exists in f16x3 only
+        (cg, F16, gather(fin=bad_fin)),
+        (mg, F16, pool_gn(c=10)),                   # c % groups
+        (mg, F16, pool_gn(c=8192, groups=32)),      # c > 4096
+        (mg, F16, pool_gn(scale=NULL)),
+    ]
+
+
 def test_degenerate_sizes_are_einval(L):
     lib = L.lib()
     x = torch.zeros(64, device="cuda")
@@ -60,6 +113,13 @@ def test_degenerate_sizes_are_einval(L):
     for name, args in calls.items():
         rc = getattr(lib, name)(*args)
         assert rc == -22, (name, rc)
+    try:
+        for k, (name, terms, args) in enumerate(_pointwise_refusals(p, L.ptr(x[1:]), s)):
+            assert lib.p2pb_set_split_terms_thread(terms) == 0
+            rc = getattr(lib, name)(*args)
+            assert rc == -22, (k, name, rc)
+    finally:
+        lib.p2pb_set_split_terms_thread(0)
     with pytest.raises(L.P2PBError):
         L.call("p2pb_furthest_point_sampling", _i(0), _i(8), _i(2), p, NULL, p, s)
     assert issubclass(L.P2PBError, RuntimeError)

@@ -1,4 +1,4 @@
-"""The fused inference kernels (csrc/pointwise.hip, csrc/conv3d.hip) against plain torch references of the
+"""The fused inference kernels (csrc/pointwise*.hip, csrc/conv3d.hip) against plain torch references of the
 same operator chains (models/pvcnn.py:162-205 SharedMLP, :414 neighbour max, :923,930 Pnet2Stage pools,
 :109-125 PVConv voxel convs). Floating point: tolerance 1e-4 relative to the tensor scale (north_star)."""
 import pytest
@@ -457,7 +457,7 @@ def test_set_abstraction_last_layer_on_the_gathered_operand(fused, B, N, M, U, C
 @pytest.mark.parametrize("b,ci,co,wide", [(16, 1024, 13184, 0), (32, 1024, 2048, 0), (2, 64, 64, 0), (5, 256, 512, 128), (1, 1024, 96, 0),
                                           (33, 128, 77, 0)])
 def test_linear_rows_matches_fp64(b, ci, co, wide):
-    """fused.linear_rows (csrc/pointwise.hip linear_rows_kernel: the per-evaluation nn.Linear layers without BLAS) vs float64:
+    """fused.linear_rows (csrc/pointwise_act.hip linear_rows_kernel: the per-evaluation nn.Linear layers without BLAS) vs float64:
     batch chunks (b > 16), a column slice of a wider weight (the global embedding's per-sample bias reads w[:, c1:]), ragged
     channel counts, with and without bias"""
     from p2p_bridge_amd import fused

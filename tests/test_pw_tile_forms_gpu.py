@@ -1,4 +1,4 @@
-"""The wide forms of the split-operand 1x1 GEMM (csrc/pointwise.hip): pw_split_kernel<WM=4> and the ping-pong
+"""The wide forms of the split-operand 1x1 GEMM (csrc/pointwise_split.hip): pw_split_kernel<WM=4> and the ping-pong
 kernel of csrc/pw_pp512.h -- which production only picks for grids of >= 1024 workgroups --
 forced here on small shapes: ragged channel / position counts, an odd number of 128-channel blocks, the folded operand
 transform, both pooling epilogues and the statistics, against float64 references of the same layer
@@ -9,6 +9,7 @@ import subprocess
 import sys
 
 import pytest
+import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -134,3 +135,81 @@ def test_pp512_kernel_shapes():
     env = dict(os.environ, P2PB_EXPERIMENT="pw_wm=4;pw_pp=1")
     r = subprocess.run([sys.executable, "-c", P5_CODE], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "PP512-OK" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+
+
+def _swish(x):
+    return x * torch.sigmoid(x)
+
+
+def _layer64(x, conv, sc, sh, bias_b):
+    """float64 reference of one folded layer, sample by sample (the largest row's output is 268 MB in float64)"""
+    w, bias = conv.weight.double().flatten(1), conv.bias.double()
+    for b in range(x.shape[0]):
+        xin = _swish(x[b].double() * sc[b, :, None].double() + sh[b, :, None].double())
+        yield b, w @ xin + (bias + bias_b[b].double())[:, None]
+
+
+def test_dispatch_table(monkeypatch):
+    """Which kernel form each kind of layer takes in production -- no P2PB_EXPERIMENT: the library reads pw_wm / pw_pp once
+    per process --, read back from the form table after every call (csrc/common.h P2PB_FORM_PW_*; the choice is made in
+    csrc/pointwise.hip pw_run / pw_run_split), and every row's output against float64 with test_256_channel_forms' bound
+    (1e-5 of the output's scale), so that the right kernel with the wrong arguments fails too.
+    Forms 2, 5 and 6 (pw_wide_kernel on the split pack, pw_pp512_kernel, the gathered operand) exist in the f16x3 arithmetic
+    only: under P2PB_CONV_MATH=bf16x6 the rows that expect 5 run pw_split_kernel<WM = 4> (4) and the rows that expect 2 or 6
+    are left out. 192 -> 512 is in whole 64-channel stages (192 = 3 * 64), so at 1024 workgroups it takes the ping-pong kernel;
+    160 -> 512 is the layer that qualifies for 256-channel workgroups and not for ping-pong (cin % 64 != 0)."""
+    from p2p_bridge_amd import fused, _lib
+    f16 = os.environ.get("P2PB_CONV_MATH", "f16x3") == "f16x3"
+    pp = 5 if f16 else 4
+    monkeypatch.setattr(fused, "PW_SPLIT_MIN_CIN", 64)  # lets pw_conv put the 64 -> 512 rows on the split pack (flags 4)
+    form = lambda ci, co, P: _lib.lib().p2pb_debug_pointwise_form(ci, co, P, None)  # noqa: E731
+    torch.manual_seed(3)
+    rows = [  # (B, cin, cout, P, keywords of pw_conv, expected form)
+        (1, 8, 8, 30, dict(math="fp32"), 0),             # fp32 pack, rows not in whole quads
+        (1, 8, 8, 32, dict(math="fp32"), 1),             # fp32 pack, 16-byte rows
+        (1, 16, 8, 32, dict(), 2),                       # flags 4 | 128
+        (1, 128, 128, 256, dict(), 3),
+        (8, 160, 512, 8192, dict(), 4),                  # exactly 1024 workgroups of 128 x 256; cin % 64 != 0
+        (7, 160, 512, 8192, dict(), 3),                  # 896 workgroups
+        (8, 192, 512, 8192, dict(), pp),
+        (7, 192, 512, 8192, dict(), 3),
+        (8, 64, 512, 8192, dict(), pp),
+        (8, 64, 512, 8192, dict(pool_u=32), 4),          # ping-pong has only the global pool
+        (8, 64, 512, 8192, dict(point_major=True, stats=False), 3),
+    ]
+    with torch.no_grad():
+        for (B, ci, co, P, kw, want) in rows:
+            if want == 2 and not f16:
+                continue
+            _lib.lib().p2pb_debug_pointwise_form(-1, 0, 0, None)
+            x = torch.randn(B, ci, P, device="cuda")
+            conv = torch.nn.Conv1d(ci, co, 1).cuda()
+            sc, sh = torch.rand(B, ci, device="cuda") + 0.5, torch.randn(B, ci, device="cuda")
+            bias_b = torch.randn(B, co, device="cuda")
+            res = fused.pw_conv(x, conv, sc, sh, swish=True, bias_b=bias_b, **kw)
+            assert form(ci, co, P) == want, (B, ci, co, P, kw, form(ci, co, P))
+            y = res[0].transpose(1, 2) if kw.get("point_major") else res[0]
+            err = mmerr = scale = 0.0
+            for b, ref in _layer64(x, conv, sc, sh, bias_b):
+                scale = max(scale, ref.abs().max().item())
+                err = max(err, (y[b].double() - ref).abs().max().item())
+                if "pool_u" in kw:
+                    g = ref.view(co, P // kw["pool_u"], kw["pool_u"])
+                    mmerr = max(mmerr, (res[2][b, ..., 0].double() - g.min(2).values).abs().max().item(),
+                                (res[2][b, ..., 1].double() - g.max(2).values).abs().max().item())
+            assert err < 1e-5 * scale and mmerr < 1e-5 * scale, (B, ci, co, P, kw, err, mmerr, scale)
+        if f16:  # the gather entry point: operand[ci, (m, u)] = zt[idx[m, u], ci] - cxt[m, ci], only {min, max} over u come out
+            B, ci, co, n, m, u = 2, 8, 16, 16, 4, 4
+            _lib.lib().p2pb_debug_pointwise_form(-1, 0, 0, None)
+            zt, cxt = torch.randn(B, n, ci, device="cuda"), torch.randn(B, m, ci, device="cuda")
+            idx = torch.randint(0, n, (B, m, u), device="cuda", dtype=torch.int32)
+            conv = torch.nn.Conv1d(ci, co, 1).cuda()
+            sc, sh = torch.rand(B, ci, device="cuda") + 0.5, torch.randn(B, ci, device="cuda")
+            _, mm = fused.pw_conv_pool_gather(zt, cxt, idx, conv, sc, sh, swish=True)
+            assert form(ci, co, m * u) == 6, form(ci, co, m * u)
+            grouped = torch.stack([zt[b][idx[b].long()] for b in range(B)]) - cxt[:, :, None, :]  # [B, m, u, ci]
+            x = grouped.permute(0, 3, 1, 2).reshape(B, ci, m * u)
+            for b, ref in _layer64(x, conv, sc, sh, torch.zeros(B, co, device="cuda")):
+                g, scale = ref.view(co, m, u), ref.abs().max().item()
+                assert (mm[b, ..., 0].double() - g.min(2).values).abs().max().item() < 1e-5 * scale
+                assert (mm[b, ..., 1].double() - g.max(2).values).abs().max().item() < 1e-5 * scale

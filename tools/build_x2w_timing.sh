@@ -4,8 +4,9 @@
 R=$(cd $(dirname $0)/..; pwd); B=$R/p2p_bridge_amd/csrc/build
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -munsafe-fp-atomics -Wno-unused-function -DP2PB_X2W_TIMING"
 mkdir -p /tmp/x2w $R/tools/exp
-for s in $R/p2p_bridge_amd/csrc/conv3d*.hip; do ( /opt/rocm/bin/hipcc $F -c $s -o /tmp/x2w/$(basename $s .hip).o ) & done  # every convolution object
-( /opt/rocm/bin/hipcc $F -c $R/p2p_bridge_amd/csrc/pointwise.hip -o /tmp/x2w/pointwise.o ) &
+for s in $R/p2p_bridge_amd/csrc/conv3d*.hip $R/p2p_bridge_amd/csrc/pointwise*.hip; do  # every convolution and pointwise object
+  ( /opt/rocm/bin/hipcc $F -c $s -o /tmp/x2w/$(basename $s .hip).o ) &
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/exp/lib_x2w.so /tmp/x2w/*.o \
-  $(ls $B/*.o | grep -v "/conv3d[^/]*\.o\|/pointwise.o") && echo built lib_x2w
+  $(ls $B/*.o | grep -v "/conv3d[^/]*\.o\|/pointwise[^/]*\.o") && echo built lib_x2w
