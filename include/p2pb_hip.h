@@ -575,10 +575,11 @@ int p2pb_se_gate_backward(int b, int c, int hidden, const float *mean, const flo
 int p2pb_row_max_forward(long rows, int u, const float *x, float *y, int *idx, void *stream);
 int p2pb_row_max_backward(long rows, int u, const float *gy, const int *idx, float *gx, void *stream);
 
-/* ---- training: weight gradients of the dense layers (csrc/wgrad.hip) --------------------------------------
+/* ---- training: weight gradients of the dense layers (csrc/wgrad*.hip) -------------------------------------
  * What cuDNN / cuBLAS compute in the reference's backward pass for nn.Conv3d(k 3, pad 1) (models/pvcnn.py:265-282)
- * and the k = 1 Conv1d / Conv2d layers (models/pvcnn.py:162-205, 803-823): exact-fp32 MFMA GEMMs over the voxel /
- * position index, split over K with a deterministic reduction (ws = scratch for the partials).
+ * and the k = 1 Conv1d / Conv2d layers (models/pvcnn.py:162-205, 803-823): MFMA GEMMs over the voxel / position index
+ * in the arithmetic `math` names (split bf16 operands by default), split over K with a deterministic reduction
+ * (ws = scratch for the partials).
  *   x f32[b,cin,r,r,r], dy f32[b,cout,r,r,r]  ->  dw f32[cout,cin,3,3,3], db f32[cout] (db may be NULL); r in {4,8,16,32}
  *   x f32[b,cin,npos],  dy f32[b,cout,npos]   ->  dw f32[cout,cin],       db f32[cout] (db may be NULL)
  * (data gradients: p2pb_conv3d_k3_forward_ex on dy with the point-reflected, channel-swapped weight;

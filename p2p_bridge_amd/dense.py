@@ -7,7 +7,8 @@ left them on torch / MIOpen in training.
     forward   the inference kernels (csrc/conv3d.hip split-operand implicit GEMM, csrc/pointwise*.hip GEMMs), plain mode
     dX        the SAME forward kernels on dY with a transformed weight: taps flipped + channel roles swapped for the
               convolution (a correlation's adjoint is the correlation with the point-reflected kernel), W^T for 1x1
-    dW, db    csrc/wgrad.hip: split-K exact-fp32 MFMA GEMMs over the voxel / position index, deterministic reduction
+    dW, db    csrc/wgrad*.hip: split-K MFMA GEMMs over the voxel / position index on bf16 terms of the operands (bf16x3 by
+              default, bf16x6 or exact fp32: train_math), deterministic reduction
 
 The parameters stay ordinary nn.Conv3d / nn.Conv1d / nn.Conv2d modules (reference checkpoint names); only the
 function applied to them changes. Transformed / packed weights are cached per parameter version.
@@ -28,7 +29,7 @@ _MATH = {"bf16x3": 0, "bf16x6": 1, "fp32": 2}
 
 
 def train_math() -> int:
-    """arithmetic of the weight-gradient GEMMs (csrc/wgrad.hip), P2PB_TRAIN_MATH: "bf16x3" (default) = torch's "high"
+    """arithmetic of the weight-gradient GEMMs (csrc/wgrad*.hip), P2PB_TRAIN_MATH: "bf16x3" (default) = torch's "high"
     float32 matmul precision, which the reference's train.py:221 selects (its cuDNN / cuBLAS kernels then run TF32);
     "bf16x6" = fp32-faithful split operands like the forward kernels; "fp32" = the exact-fp32 MFMA kernels"""
     import os
@@ -168,7 +169,7 @@ class _Conv3dK3(torch.autograd.Function):
             def wgrad():
                 gw = torch.empty(co, ci, 3, 3, 3, dtype=F32, device=x.device)
                 gb = torch.empty(co, dtype=F32, device=x.device) if want_b else None
-                if occ is not None:  # x is zero outside the occupied voxels: K = occupied voxels (csrc/wgrad.hip, exact fp32)
+                if occ is not None:  # x is zero outside the occupied voxels: K = occupied voxels (csrc/wgrad_occ.hip, exact fp32)
                     cnt, npts = occ
                     ws = torch.empty(lib().p2pb_conv3d_k3_wgrad_occ_ws_floats(_i(b), _i(ci), _i(co), _i(r), _i(npts)), dtype=F32,
                                      device=x.device)

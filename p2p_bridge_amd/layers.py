@@ -137,7 +137,7 @@ class NeighborInterpolation(Function):
 class Occupancy:
     """Which voxels of ONE particular grid tensor can be non-zero: the voxelisation's counts i32[B, r^3] and the points per
     cloud, tied to the tensor they describe by its storage pointer and its version counter AT THE TIME IT WAS PRODUCED. A
-    consumer (dense.conv3d_k3's occupied-voxel weight gradient, csrc/wgrad.hip) must call `describes(x)` first: any in-place
+    consumer (dense.conv3d_k3's occupied-voxel weight gradient, csrc/wgrad_occ.hip) must call `describes(x)` first: any in-place
     edit of the grid (`v.add_`, `dropout_`, ...) bumps the version, any out-of-place op yields another tensor, and in both
     cases the grid may be non-zero where counts == 0 -- the consumer then takes the dense path."""
 

@@ -138,3 +138,26 @@ def test_tensor_preconditions_raise_runtime_error():
     with pytest.raises(RuntimeError, match="float"):
         ext.furthest_point_sampling_forward(c.double(), 8)
     assert ext.furthest_point_sampling_forward(c, 8).shape == (2, 8)
+
+
+# (b, cin, cout, r | npos) -> K-splits under math 0 and 1 (bf16x3, bf16x6), under math 2 (exact fp32)
+_WGRAD_CONV_SPLITS = {(8, 64, 64, 32): (113, 113), (8, 128, 64, 16): (56, 56), (8, 256, 256, 8): (7, 7), (2, 8, 16, 4): (8, 2),
+                      (1, 8, 16, 4): (4, 1), (2, 512, 512, 8): (1, 1), (3, 3, 70, 8): (48, 6), (64, 256, 256, 32): (7, 7),
+                      (2, 35, 32, 32): (170, 192)}
+_WGRAD_PW_SPLITS = {(2, 3, 128, 1000): (32, 8), (2, 512, 1024, 2048): (4, 4), (2, 67, 64, 333): (42, 4), (2, 64, 64, 17): (4, 2),
+                    (1, 256, 384, 8): (1, 1), (8, 128, 3, 2048): (192, 64), (2, 1024, 1024, 128): (2, 2), (1, 64, 64, 3): (1, 1)}
+
+
+def test_wgrad_plan(L):
+    """The workspace of a dense weight gradient (csrc/wgrad.hip: conv_wgrad_plan, pw_wgrad_plan) is whole partial rows -- cout * cin *
+    taps weights + cout bias sums -- one per K-split. The split counts are pinned for every limit of the plan (the chip-filling
+    target, the 48 MB of partials, the K units of the form that runs, the cap of 192) under the three kernel forms: host-only
+    calls, nothing is launched."""
+    lib = L.lib()
+    for name, taps, table in (("p2pb_conv3d_k3_wgrad_ws_floats", 27, _WGRAD_CONV_SPLITS),
+                              ("p2pb_pointwise_wgrad_ws_floats", 1, _WGRAD_PW_SPLITS)):
+        for (b, cin, cout, n), (ns_bf16, ns_fp32) in table.items():
+            row = cout * cin * taps + cout
+            for math, ns in ((0, ns_bf16), (1, ns_bf16), (2, ns_fp32)):
+                floats = getattr(lib, name)(_i(b), _i(cin), _i(cout), _i(n), _i(math))
+                assert floats % row == 0 and floats // row == ns, (name, b, cin, cout, n, math, floats / row)

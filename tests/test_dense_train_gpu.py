@@ -1,4 +1,4 @@
-"""Hand-written dense forward / backward for training (p2p_bridge_amd/dense.py, csrc/wgrad.hip): the 3x3x3 voxel
+"""Hand-written dense forward / backward for training (p2p_bridge_amd/dense.py, csrc/wgrad*.hip): the 3x3x3 voxel
 convolution and the k=1 convolutions as autograd Functions vs torch's own fp64 autograd of the same op."""
 import pytest
 import torch
@@ -49,7 +49,10 @@ def test_conv3d_k3_forward_backward(b, ci, co, r, math, monkeypatch):
 @pytest.mark.parametrize("math", ["bf16x3", "bf16x6", "fp32"])
 @pytest.mark.parametrize("b,ci,co,shape", [(2, 3, 128, (1000,)), (2, 512, 1024, (2048,)), (3, 67, 64, (128, 32)),
                                            (2, 832, 256, (128,)), (8, 128, 3, (2048,)), (2, 35, 32, (512, 32)),
-                                           (1, 256, 384, (8, 1)), (2, 320, 256, (8, 32))])
+                                           (1, 256, 384, (8, 1)), (2, 320, 256, (8, 32)),
+                                           # rows that are no whole 16-byte pieces (pointwise_wgrad_bf16_kernel under the bf16 maths):
+                                           # a ragged tail, one K unit of 16 plus a tail, less than one fragment of 8
+                                           (2, 67, 64, (333,)), (2, 64, 64, (17,)), (1, 64, 64, (3,))])
 def test_pointwise_forward_backward(b, ci, co, shape, math, monkeypatch):
     from p2p_bridge_amd import dense
 
@@ -70,6 +73,11 @@ def test_pointwise_forward_backward(b, ci, co, shape, math, monkeypatch):
     assert _rel(x.grad.reshape(b, ci, -1), x64.grad) < XTOL[math]
     assert _rel(conv.weight.grad.reshape(co, ci), w64.grad) < WTOL[math]
     assert _rel(conv.bias.grad, b64.grad) < 5e-6
+    # deterministic: the same inputs again give the same bits (fixed K-splits, partials added in split order)
+    gw, gb = conv.weight.grad.clone(), conv.bias.grad.clone()
+    conv.weight.grad = conv.bias.grad = None
+    dense.pointwise(x, conv).backward(gy)
+    assert torch.equal(conv.weight.grad, gw) and torch.equal(conv.bias.grad, gb)
 
 
 @pytest.mark.parametrize("conv_math", ["fp32", "bf16x6", "f16x3"])
@@ -216,7 +224,7 @@ def test_conv_norm_act_forward_backward(kind, b, ci, co, shape, swish):
 @pytest.mark.parametrize("b,ci,co,r,n", [(3, 35, 32, 32, 2048), (2, 64, 64, 32, 1500), (4, 128, 64, 16, 512), (2, 24, 40, 16, 300),
                                          (1, 8, 8, 32, 1)])
 def test_sparse_weight_gradient_of_a_first_convolution(b, ci, co, r, n):
-    """round 5 (csrc/wgrad.hip conv3d_k3_wgrad_occ_kernel): the weight gradient of a PVConv's first convolution over the occupied
+    """round 5 (csrc/wgrad_occ.hip conv3d_k3_wgrad_occ_kernel): the weight gradient of a PVConv's first convolution over the occupied
     voxels only -- x = avg_voxelize(features) is zero elsewhere -- against torch's fp64 convolution backward and against the dense
     kernel; grid-boundary voxels, ragged channel counts, a single point"""
     from p2p_bridge_amd import dense, layers as L

@@ -1,4 +1,4 @@
-"""micro-benchmark of the weight-gradient kernels (csrc/wgrad.hip) at the config-3 layer shapes (B = 8):
+"""micro-benchmark of the weight-gradient kernels (csrc/wgrad_bf16.hip, wgrad_fp32.hip; planned and reduced by wgrad.hip) at the config-3 layer shapes (B = 8):
 per math mode the time per launch and the algorithmic TFLOP/s (2 * B * r^3 * 27 * Cin * Cout)"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
