@@ -61,7 +61,7 @@ int p2pb_set_split_terms(int terms);
  * threads' launches and weight packs do not see; p2pb_get_split_terms returns what a launch from this thread would use */
 int p2pb_set_split_terms_thread(int terms);
 int p2pb_get_split_terms(void);
-/* Deterministic mode (process-wide, default off): the scatter-add backward passes (p2pb_trilinear_devoxelize_backward,
+/* Deterministic mode (process-wide, default off): the scatter-add backward passes (csrc/scatter_grad.hip: p2pb_trilinear_devoxelize_backward,
  * p2pb_grouping_backward, p2pb_three_nn_interpolate_backward -- the adjoints of PN2/trilinear_devox_gpu.cu:111,
  * pvcnn_grouping_gpu.cu:51, pvcnn_neighbor_interpolate_gpu.cu:101, whose float atomicAdd order is arbitrary in the reference
  * too) accumulate in a fixed order -- one wave per workgroup over rows held in LDS -- so that a training run is bit-reproducible;

@@ -17,7 +17,7 @@ __all__ = ["install_dropin", "deterministic"]
 
 class deterministic:
     """`with p2p_bridge_amd.deterministic():` (or `deterministic(True)` / `(False)` as a call) -- bit-reproducible training:
-    the scatter-add backward passes accumulate in a fixed order (include/p2pb_hip.h p2pb_set_deterministic) and torch's
+    the scatter-add backward passes (csrc/scatter_grad.hip) accumulate in a fixed order (include/p2pb_hip.h p2pb_set_deterministic) and torch's
     own kernels run under torch.use_deterministic_algorithms(warn_only=True). Slower; off by default, as in the reference
     (whose CUDA backward kernels are float-atomic scatters as well)."""
 

@@ -26,7 +26,7 @@ extern "C" int p2pb_set_split_terms_thread(int terms) {  // 0 clears the calling
 }
 extern "C" int p2pb_get_split_terms(void) { return p2pb_split_terms_now(); }  // what a launch from THIS thread would use
 
-// Deterministic mode (process-wide): the scatter-add backward passes (devoxelise, grouping, three-NN interpolation) accumulate
+// Deterministic mode (process-wide): the scatter-add backward passes (scatter_grad.hip: devoxelise, grouping, three-NN interpolation) accumulate
 // their LDS rows with ONE wave per workgroup, so every destination receives its contributions in program order (ascending source
 // index; the lanes of one ds_add_f32 are served in lane order) instead of in the arrival order of 8 waves. Slower (those passes
 // 0.6 -> ~4 ms per config-3 step), bit-reproducible from run to run; rows that do not fit the LDS are refused (P2PB_EINVAL)

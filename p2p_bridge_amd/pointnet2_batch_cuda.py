@@ -90,7 +90,7 @@ def trilinear_devoxelize_backward(grad_y, indices, weights, r):
     except P2PBError as e:
         if not lib().p2pb_get_deterministic():
             raise
-        # (the library refuses a grid row beyond the LDS -- csrc/common.h SCAT_LDS_MAX, scat_rows -- in deterministic mode: only
+        # (the library refuses a grid row beyond the LDS -- csrc/scatter_grad.hip SCAT_LDS_MAX, scat_rows -- in deterministic mode: only
         #  the global-atomic kernel, whose order is not fixed, would be left)
         raise P2PBError(f"trilinear_devoxelize_backward: no deterministic kernel for r = {r} (r^3 = {r3} voxels per grid row, "
                            "beyond what the fixed-order kernel holds in LDS): train this resolution outside "

@@ -2,10 +2,9 @@
 three_nearest_neighbors_interpolate_backward(_pitched), gather_features_backward -- against a float64 restatement of each adjoint
 written here (gx[b, ch, idx] += w * gy with scatter_add_ on the CPU), on every kernel form of their dispatch and in both modes.
 
-Forms: the `switch` after scat_rows(L, c, cap) (csrc/common.h "scatter-add backward passes"; csrc/voxelize.hip
-p2pb_trilinear_devoxelize_backward, csrc/neighbors.hip p2pb_grouping_backward_pitched and
-p2pb_three_nn_interpolate_backward_pitched) picks an LDS-row kernel with CH in {1, 2, 4, 8} (devoxelisation: and 16) rows per
-workgroup, or the global-atomic kernel for rows beyond 128 KiB (form 0 here). `scat_rows` and the three switches are restated
+Forms: scat_grad (csrc/scatter_grad.hip, the one host function behind all of these entry points) rounds scat_rows(L, c, cap)
+down to a power of two and launches scat_grad_lds_kernel<K, W, CH> with CH in {1, 2, 4, 8} (devoxelisation: and 16) rows per
+workgroup, or the global-atomic scat_grad_kernel for rows beyond 128 KiB (form 0 here). `scat_rows` and that rule are restated
 below, and the case tables are held to them where they are made: a table that stops reaching a form fails at import.
 
 Inputs are built directly (indices and weights are arguments of these ops) and every index is in range. Outputs are carved from a
@@ -43,18 +42,25 @@ PATTERNS = ("uniform", "half0", "one", "dup", "zerow", "ends")
 
 
 def scat_rows(L, c, cap):
-    """csrc/common.h scat_rows: rows per workgroup -- what fits 64 KiB, at most cap and c; one row up to 128 KiB; 0 = no fit"""
+    """csrc/scatter_grad.hip scat_rows: rows per workgroup -- what fits 64 KiB, at most cap and c; one row up to 128 KiB; 0 = no fit"""
     if L * 4 > SCAT_LDS_MAX:
         return 0
     return min(max((64 * 1024) // (L * 4), 1), cap, c)
 
 
 def form(op, L, c):
-    """the CH of the *_grad_lds_kernel<CH> that the operator's switch launches; 0 = the global-atomic kernel"""
+    """the CH of the scat_grad_lds_kernel<K, W, CH> that scat_grad launches: scat_rows rounded down to a power of two; 0 = the
+    global-atomic kernel"""
     ch = scat_rows(L, c, CAP[op])
-    if op == "devox":  # voxelize.hip: 1 | 2, 3 | 4..7 | 16 | default (8..15)
-        return {0: 0, 1: 1, 2: 2, 3: 2, 4: 4, 5: 4, 6: 4, 7: 4, 16: 16}.get(ch, 8)
-    return {0: 0, 1: 1, 2: 2, 3: 2, 8: 8}.get(ch, 4)  # neighbors.hip: 1 | 2, 3 | 8 | default (4..7)
+    return 1 << (ch.bit_length() - 1) if ch else 0
+
+
+# the two `switch` statements that this rule replaced (cap 16: 1 | 2, 3 | 4..7 | 16 | default; cap 8: 1 | 2, 3 | 8 | default) chose
+# the same CH for every value scat_rows can return
+for _ch in range(17):
+    _p2 = 1 << (_ch.bit_length() - 1) if _ch else 0
+    assert {0: 0, 1: 1, 2: 2, 3: 2, 4: 4, 5: 4, 6: 4, 7: 4, 16: 16}.get(_ch, 8) == _p2, _ch
+    assert _ch > 8 or {0: 0, 1: 1, 2: 2, 3: 2, 8: 8}.get(_ch, 4) == _p2, _ch
 
 
 FORMS = {"devox": (0, 1, 2, 4, 8, 16), "group": (0, 1, 2, 4, 8), "interp": (0, 1, 2, 4, 8)}

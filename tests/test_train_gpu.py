@@ -213,7 +213,7 @@ def test_punet_paired_patches_on_device(tmp_path):
 def test_deterministic_mode_makes_training_bit_reproducible(graph):
     """`with p2p_bridge_amd.deterministic():` -- two training runs of stock PVDS (8 x 2048 points, 6 optimiser steps, eager and
     as the captured step) from the same seed end in BITWISE equal weights: the scatter-add backward passes (devoxelise, grouping,
-    three-NN interpolation) accumulate in a fixed order (include/p2pb_hip.h p2pb_set_deterministic); everything else on the
+    three-NN interpolation: csrc/scatter_grad.hip) accumulate in a fixed order (include/p2pb_hip.h p2pb_set_deterministic); everything else on the
     training path already reduces in a fixed order. The reference has no such mode (its backward kernels are float atomicAdd
     scatters); tests/test_full_size_parity_gpu.py trains its gated denoiser under it."""
     import p2p_bridge_amd
