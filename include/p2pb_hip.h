@@ -30,7 +30,8 @@ extern "C" {
 
 #define P2PB_EINVAL (-22)
 
-/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (10: the GroupNorm finisher is
+/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (11: the five
+ * p2pb_pn2_* operators added; 10: the GroupNorm finisher is
  * passed to p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather as fin_* arguments, the three
  * entry points that armed one for the thread's next launch removed; 9: the set metrics
  * p2pb_pairwise_chamfer / p2pb_pairwise_emd / p2pb_occupancy_* added; 8: p2pb_softmax_attention_* added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
@@ -38,7 +39,7 @@ extern "C" {
  * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
  * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
-#define P2PB_ABI_VERSION 10
+#define P2PB_ABI_VERSION 11
 
 /* library / device info --------------------------------------------------------------------- */
 int p2pb_version(void);            /* == P2PB_ABI_VERSION of the header the library was built from */
@@ -199,6 +200,37 @@ int p2pb_three_nn_interpolate_backward(int b, int c, int n, int m, const float *
 /* (gy_pitch >= c*n: as p2pb_grouping_backward_pitched; the slice of models/pvcnn.py:219's concatenation) */
 int p2pb_three_nn_interpolate_backward_pitched(int b, int c, int n, int m, const float *grad_y, long gy_pitch, const int *idx,
                                                const float *w, float *grad_x, void *stream);
+
+/* ---- the classic PointNet++ operators of the same extension (csrc/pointnet2_legacy.hip) ------------------------------
+ * Replace the launchers behind ball_query_wrapper, three_nn_wrapper, furthest_point_sampling_wrapper,
+ * three_interpolate_wrapper and three_interpolate_grad_wrapper (PN2/pointnet2_api.cpp:17-29; kernels PN2/ball_query_gpu.cu:15,
+ * interpolate_gpu.cu:16,84,127, sampling_gpu.cu:101). Clouds are POINT-major f32[b,n,3], features channel-major; argument
+ * order is the reference launchers'. THE CALLER ALLOCATES AND INITIALISES EVERY OUTPUT, as the reference's layers do
+ * (third_party/openpoints/models/layers/{group,subsample,upsampling}.py). Squared distances: fma(dz,dz, fma(dy,dy, dx*dx)).
+ * (group_points* / gather_points* of that list are p2pb_grouping_* / p2pb_gather_features_* above.)
+ *
+ * p2pb_pn2_ball_query: new_xyz f32[b,m,3], xyz f32[b,n,3] -> idx i32[b,m,nsample]: the first nsample points k (ascending)
+ *   with d2 < radius*radius (float product, strict); the first hit fills every slot, later hits overwrite slots 1, 2, ...
+ *   A centre with no neighbour LEAVES ITS ROW UNTOUCHED (the layer zero-fills idx before the call).
+ * p2pb_pn2_three_nn: unknown f32[b,n,3], known f32[b,m,3] -> dist2 f32[b,n,3] (SQUARED distances, ascending), idx i32[b,n,3];
+ *   strict '<' in ascending k (equal distances: lower index first); for m < 3 the unfilled slots are idx 0, dist2 +inf.
+ * p2pb_pn2_fps: xyz f32[b,n,3], temp f32[b,n] IN/OUT (running minima; the layer fills it with 1e10) -> idx i32[b,m].
+ *   idx[:,0] = 0; round j = 1..m-1 does temp[k] = min(temp[k], d2(k, idx[j-1])) and picks the maximum of temp in the order
+ *   (temp desc, k mod T asc, k asc), T = min(2^floor(log2 n), 1024): the reference's block size and lower-thread-wins tree
+ *   (1024, not the 512 of p2pb_furthest_point_sampling). On return temp holds the minima over samples 0..m-2. m == 0 writes
+ *   nothing. Any n (n <= 16384: registers; above: temp is the working array, one workgroup streaming the cloud).
+ * p2pb_pn2_three_interpolate: features f32[b,c,m], idx i32[b,n,3], weight f32[b,n,3] -> out f32[b,c,n] =
+ *   fma(f[idx2], w2, fma(f[idx1], w1, f[idx0] * w0)).
+ * p2pb_pn2_three_interpolate_grad: grad_out f32[b,c,n] -> grad_features f32[b,c,m] += grad_out * w_k at idx_k (fp32 global
+ *   atomics; ACCUMULATES, the layer passes zeros). Refused (P2PB_EINVAL) in deterministic mode: the order is not fixed. */
+int p2pb_pn2_ball_query(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz, int *idx,
+                        void *stream);
+int p2pb_pn2_three_nn(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx, void *stream);
+int p2pb_pn2_fps(int b, int n, int m, const float *xyz, float *temp, int *idx, void *stream);
+int p2pb_pn2_three_interpolate(int b, int c, int m, int n, const float *features, const int *idx, const float *weight,
+                               float *out, void *stream);
+int p2pb_pn2_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out, const int *idx, const float *weight,
+                                    float *grad_features, void *stream);
 
 /* chamfer_3D: replaces chamfer_cuda_forward/backward (metrics/chamfer3D/chamfer3D.cu:135,176;
  * kernels :12,:155). xyz are POINT-major f32[b,n,3] / f32[b,m,3]. Lowest index wins distance ties.

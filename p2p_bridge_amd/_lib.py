@@ -37,9 +37,10 @@ SYMBOLS = [
     "p2pb_se_gate_forward", "p2pb_se_gate_backward", "p2pb_row_max_forward", "p2pb_row_max_backward",
     "p2pb_pairwise_chamfer_ws_bytes", "p2pb_pairwise_chamfer", "p2pb_pairwise_emd_ws_bytes", "p2pb_pairwise_emd",
     "p2pb_occupancy_grid_cells", "p2pb_occupancy_ws_bytes", "p2pb_occupancy_counts",
+    "p2pb_pn2_ball_query", "p2pb_pn2_three_nn", "p2pb_pn2_fps", "p2pb_pn2_three_interpolate", "p2pb_pn2_three_interpolate_grad",
 ]
 
-ABI_VERSION = 10  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
+ABI_VERSION = 11  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
 
 _lib = None
 

@@ -1,0 +1,419 @@
+// pointnet2_legacy.hip -- the classic PointNet++ operators of the reference's extension, on its POINT-MAJOR clouds
+// (xyz f32[B,N,3]; PN2 = third_party/openpoints/cpp/pointnet2_batch/src):
+//   p2pb_pn2_ball_query              (PN2/ball_query_gpu.cu:15)
+//   p2pb_pn2_three_nn                (PN2/interpolate_gpu.cu:16)
+//   p2pb_pn2_fps                     (PN2/sampling_gpu.cu:101)
+//   p2pb_pn2_three_interpolate       (PN2/interpolate_gpu.cu:84)
+//   p2pb_pn2_three_interpolate_grad  (PN2/interpolate_gpu.cu:127)
+// The caller owns every output; the gradient ADDS into its target. group_points* / gather_points* of the same extension
+// have the layout and arithmetic of p2pb_grouping_* / p2pb_gather_features_* (neighbors.hip, scatter_grad.hip) and are
+// routed there by the Python module. Squared distances are sqdist3 (common.h), as everywhere in the library.
+#include "common.h"
+
+typedef unsigned long long u64;
+
+// ------------------------------------------------------------------------------------------------
+// ball query: one wave per centre, ballot + mbcnt ordered slots as ball_query_lds_kernel (neighbors.hip), the cloud
+// staged in LDS as three planes when it fits and there are enough centres to share it. What differs from the
+// channel-major operator is the contract: a centre without a neighbour leaves its row as the caller filled it
+// (PN2/ball_query_gpu.cu:40-49 writes on a hit only).
+// ------------------------------------------------------------------------------------------------
+#define PN2_BQ_UNROLL 4
+template <bool LDS>
+__global__ __launch_bounds__(1024) void pn2_ball_query_kernel(int n, int m, float r2, int u, int cpw,
+                                                              const float *__restrict__ new_xyz,
+                                                              const float *__restrict__ xyz, int *__restrict__ idx) {
+  extern __shared__ float pn2_bq_pts[];  // [3][n] when LDS
+  const int b = blockIdx.y;
+  const int lane = lane_id(), wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const float *p = xyz + (size_t)b * 3 * n;
+  const float *ce = new_xyz + (size_t)b * 3 * m;
+  if (LDS) {
+    for (int k = threadIdx.x; k < 3 * n; k += blockDim.x) pn2_bq_pts[(k % 3) * n + k / 3] = p[k];
+    __syncthreads();
+  }
+  const int j0 = (blockIdx.x * nwaves + wave) * cpw;
+  for (int j = j0; j < min(j0 + cpw, m); ++j) {
+    int *o = idx + ((size_t)b * m + j) * u;
+    const float cx = ce[3 * j], cy = ce[3 * j + 1], cz = ce[3 * j + 2];
+    int cnt = 0, first = 0;
+    for (int base = 0; base < n && cnt < u; base += 64 * PN2_BQ_UNROLL) {
+      float px[PN2_BQ_UNROLL], py[PN2_BQ_UNROLL], pz[PN2_BQ_UNROLL];
+#pragma unroll
+      for (int q = 0; q < PN2_BQ_UNROLL; ++q) {
+        const int k = min(base + q * 64 + lane, n - 1);
+        if (LDS) {
+          px[q] = pn2_bq_pts[k];
+          py[q] = pn2_bq_pts[n + k];
+          pz[q] = pn2_bq_pts[2 * n + k];
+        } else {
+          px[q] = p[(size_t)3 * k];
+          py[q] = p[(size_t)3 * k + 1];
+          pz[q] = p[(size_t)3 * k + 2];
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < PN2_BQ_UNROLL; ++q) {
+        const int k = base + q * 64 + lane;
+        const float d2 = sqdist3(cx - px[q], cy - py[q], cz - pz[q]);
+        const bool in = (k < n) && (d2 < r2);
+        const unsigned long long mask = __ballot(in);
+        if (mask) {
+          const int slot = cnt + mbcnt(mask);
+          if (in && slot < u) o[slot] = k;
+          if (cnt == 0) first = base + q * 64 + (int)__builtin_ctzll(mask);
+          cnt += (int)__builtin_popcountll(mask);
+        }
+      }
+    }
+    // the first hit fills every slot, later hits overwrite slots 1, 2, ...: slots >= cnt keep the first hit
+    if (cnt > 0)
+      for (int v = cnt + lane; v < u; v += 64) o[v] = first;
+  }
+}
+
+#define PN2_BQ_LDS_MAX (144 * 1024)
+extern "C" int p2pb_pn2_ball_query(int b, int n, int m, float radius, int nsample, const float *new_xyz, const float *xyz,
+                                   int *idx, void *stream) {
+  if (b <= 0 || b > 65535 || n <= 0 || m <= 0 || nsample <= 0 || !new_xyz || !xyz || !idx) return P2PB_EINVAL;
+  const float r2 = radius * radius;  // the float product of PN2/ball_query_gpu.cu:29
+  const size_t lds = (size_t)3 * n * sizeof(float);
+  if (lds <= PN2_BQ_LDS_MAX && (long)m * b >= 2048) {  // enough centres to share the staged cloud (the bound of p2pb_ball_query)
+    static bool once = false;
+    if (!once) {
+      (void)hipFuncSetAttribute((const void *)pn2_ball_query_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024);
+      once = true;
+    }
+    // centres per wave: about two workgroups per CU over the whole launch, at least 1 (as p2pb_ball_query)
+    int cpw = (int)(((long)m * b + 16L * 512 - 1) / (16L * 512));
+    if (cpw < 1) cpw = 1;
+    hipLaunchKernelGGL(pn2_ball_query_kernel<true>, dim3(cdiv(m, 16 * cpw), b), dim3(1024), lds, (hipStream_t)stream, n, m,
+                       r2, nsample, cpw, new_xyz, xyz, idx);
+    return p2pb_launch_status();
+  }
+  hipLaunchKernelGGL(pn2_ball_query_kernel<false>, dim3(cdiv(m, 4), b), dim3(256), 0, (hipStream_t)stream, n, m, r2,
+                     nsample, 1, new_xyz, xyz, idx);
+  return p2pb_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// three nearest known points of every unknown point: one lane per query, `known` tiled through LDS as planes and read
+// back as wave-wide broadcasts (three_nn_kernel of neighbors.hip without the weights). Strict '<' in ascending k: among
+// equal distances the lower index ranks first. The reference's bests start at 1e40 in double, which no fp32 distance
+// reaches and which its float store turns into +inf: +inf in fp32 takes the same branches, so for m < 3 the unfilled
+// slots are idx 0, dist2 +inf.
+// ------------------------------------------------------------------------------------------------
+#define PN2_NN_TILE 2048
+__global__ __launch_bounds__(256) void pn2_three_nn_kernel(int n, int m, const float *__restrict__ unknown,
+                                                           const float *__restrict__ known, float *__restrict__ dist2,
+                                                           int *__restrict__ idx) {
+  __shared__ float sc[3][PN2_NN_TILE];
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const float *un = unknown + (size_t)b * 3 * n;
+  const float *kn = known + (size_t)b * 3 * m;
+  const bool ok = j < n;
+  const float ux = ok ? un[(size_t)3 * j] : 0.0f, uy = ok ? un[(size_t)3 * j + 1] : 0.0f, uz = ok ? un[(size_t)3 * j + 2] : 0.0f;
+  float best0 = INFINITY, best1 = INFINITY, best2 = INFINITY;
+  int i0 = 0, i1 = 0, i2 = 0;
+  for (int k0 = 0; k0 < m; k0 += PN2_NN_TILE) {
+    const int kn_ = min(PN2_NN_TILE, m - k0);
+    __syncthreads();
+    for (int k = threadIdx.x; k < 3 * kn_; k += 256) sc[k % 3][k / 3] = kn[(size_t)3 * k0 + k];
+    __syncthreads();
+    for (int k = 0; k < kn_; ++k) {
+      const float d = sqdist3(ux - sc[0][k], uy - sc[1][k], uz - sc[2][k]);
+      if (d < best2) {
+        best2 = d;
+        i2 = k0 + k;
+        if (d < best1) {
+          best2 = best1;
+          i2 = i1;
+          best1 = d;
+          i1 = k0 + k;
+          if (d < best0) {
+            best1 = best0;
+            i1 = i0;
+            best0 = d;
+            i0 = k0 + k;
+          }
+        }
+      }
+    }
+  }
+  if (!ok) return;
+  float *d = dist2 + ((size_t)b * n + j) * 3;
+  int *id = idx + ((size_t)b * n + j) * 3;
+  d[0] = best0;
+  d[1] = best1;
+  d[2] = best2;
+  id[0] = i0;
+  id[1] = i1;
+  id[2] = i2;
+}
+
+extern "C" int p2pb_pn2_three_nn(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx,
+                                 void *stream) {
+  if (b <= 0 || b > 65535 || n <= 0 || m <= 0 || !unknown || !known || !dist2 || !idx) return P2PB_EINVAL;
+  hipLaunchKernelGGL(pn2_three_nn_kernel, dim3(cdiv(n, 256), b), dim3(256), 0, (hipStream_t)stream, n, m, unknown, known,
+                     dist2, idx);
+  return p2pb_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// furthest point sampling with the reference's contract: temp f32[B,N] is the caller's running minima, read on entry
+// (the layer fills it with 1e10) and written back once at the end, so it returns holding the minima over samples
+// 0 .. m-2 (the last pick starts no round).
+// Tie order: the reference's block has T(n) = min(2^floor(log2 n), 1024) threads (PN2/cuda_utils.h:10), thread t scans
+// k = t, t + T, ... keeping the first strict maximum, and its shared-memory tree keeps the lower thread on ties
+// (PN2/sampling_gpu.cu:93-98): (temp desc, k mod T asc, k asc). As in sampling.hip the order is the low word of a 64-bit
+// key, so any thread layout reproduces it; that file's key is fixed to the 512 threads of the PVCNN sampler, this one
+// takes log2 T.
+// One workgroup per cloud. n <= 16384: coordinates and minima in registers for the whole kernel, the winner's
+// coordinates from an LDS copy of the cloud when it fits; above: minima in temp itself, coordinates streamed from L2.
+// ------------------------------------------------------------------------------------------------
+// (The DPP maximum and the key helpers below restate sampling.hip's, whose device code is pinned by its bit-exact tests;
+//  one copy in common.h is the follow-up once that file may be touched.)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned pn2_umax_step(unsigned v) {
+  const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);  // (0 = identity of max)
+  return o > v ? o : v;
+}
+// max over each 16-lane row, valid in the row's lane 15
+__device__ __forceinline__ unsigned pn2_rowmax_u32(unsigned v) {
+  v = pn2_umax_step<0x111, 0xf>(v);  // row_shr:1
+  v = pn2_umax_step<0x112, 0xf>(v);  // row_shr:2
+  v = pn2_umax_step<0x114, 0xf>(v);  // row_shr:4
+  v = pn2_umax_step<0x118, 0xf>(v);  // row_shr:8
+  return v;
+}
+__device__ __forceinline__ unsigned pn2_wavemax_u32(unsigned v) {
+  v = pn2_rowmax_u32(v);
+  v = pn2_umax_step<0x142, 0xa>(v);  // row_bcast:15 into rows 1, 3
+  v = pn2_umax_step<0x143, 0xc>(v);  // row_bcast:31 into rows 2, 3 -> lane 63 holds the wave's maximum
+  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+// lexicographic maximum of 64-bit keys as two 32-bit reductions: the high words, then the low words of the lanes that
+// hold the winning high word. WAVE: over the 64 lanes; else over the first 16-lane row. Returned in every lane.
+template <bool WAVE>
+__device__ __forceinline__ u64 pn2_max_u64(u64 v) {
+  const unsigned hi = (unsigned)(v >> 32);
+  unsigned H, L;
+  if (WAVE) {
+    H = pn2_wavemax_u32(hi);
+    L = pn2_wavemax_u32(hi == H ? (unsigned)v : 0u);
+  } else {
+    H = (unsigned)__builtin_amdgcn_readlane((int)pn2_rowmax_u32(hi), 15);
+    L = (unsigned)__builtin_amdgcn_readlane((int)pn2_rowmax_u32(hi == H ? (unsigned)v : 0u), 15);
+  }
+  return ((u64)H << 32) | L;
+}
+// best > 0: its bit pattern + 1 (monotonic); 0: 1; a thread without points carries -1 -> 0, the lowest key.
+// low word: ~((k mod T) << 21 | k / T), lt = log2 T <= 10 (k / T < 2^21 for any int k)
+__device__ __forceinline__ u64 pn2_fps_key(float best, int k, int lt) {
+  const unsigned hi = best > 0.0f ? (__float_as_uint(best) + 1u) : (best == 0.0f ? 1u : 0u);
+  const unsigned sec = (((unsigned)k & ((1u << lt) - 1u)) << 21) | ((unsigned)k >> lt);
+  return ((u64)hi << 32) | (u64)(~sec);
+}
+__device__ __forceinline__ int pn2_fps_key_index(u64 key, int lt) {
+  const unsigned sec = ~(unsigned)key;
+  return (int)(((sec & 0x1FFFFFu) << lt) | (sec >> 21));
+}
+// the workgroup's maximum from the waves' maxima: one LDS slot per wave (double-buffered by round parity), one barrier,
+// and a 16-entry row reduction that every wave repeats (slots [2][16], zero = identity beyond the last wave)
+__device__ __forceinline__ u64 pn2_block_max(u64 key, u64 *slots, int j, int t) {
+  u64 *sl = slots + (j & 1) * 16;
+  if ((t & 63) == 0) sl[t >> 6] = key;
+  __syncthreads();
+  return pn2_max_u64<false>(sl[t & 15]);
+}
+
+// thread t owns k = t + i * THREADS. With PPT > 1 the launcher uses 1024 threads and n > 1024, so T = 1024: the thread's
+// points share k mod T and are visited in ascending k, and "first strict maximum" inside the thread is the tie order.
+template <int THREADS, int PPT, bool LDS_XYZ>
+__global__ __launch_bounds__(THREADS) void pn2_fps_kernel(int n, int m, int lt, const float *__restrict__ xyz,
+                                                          float *__restrict__ temp, int *__restrict__ idxs) {
+  extern __shared__ __attribute__((aligned(16))) char pn2_fps_smem[];
+  u64 *slots = (u64 *)pn2_fps_smem;                              // [2][16]
+  float *sxyz = (float *)(pn2_fps_smem + 2 * 16 * sizeof(u64));  // [n][3] when LDS_XYZ
+  const int t = threadIdx.x;
+  const float *c = xyz + (size_t)blockIdx.x * 3 * n;
+  float *tp = temp + (size_t)blockIdx.x * n;
+  int *out = idxs + (size_t)blockIdx.x * m;
+
+  float x[PPT], y[PPT], z[PPT], dist[PPT];
+#pragma unroll
+  for (int i = 0; i < PPT; ++i) {
+    const int k = t + i * THREADS;
+    const bool ok = k < n;
+    x[i] = ok ? c[3 * k] : 0.0f;
+    y[i] = ok ? c[3 * k + 1] : 0.0f;
+    z[i] = ok ? c[3 * k + 2] : 0.0f;
+    dist[i] = ok ? tp[k] : -1.0f;  // -1 = "no point here": stays -1, never selected
+  }
+  if (LDS_XYZ)
+    for (int k = t; k < 3 * n; k += THREADS) sxyz[k] = c[k];
+  if (t < 32) slots[t] = 0;
+  if (t == 0) out[0] = 0;
+  __syncthreads();
+
+  int old = 0;
+  for (int j = 1; j < m; ++j) {
+    float x1, y1, z1;
+    if (LDS_XYZ) {
+      x1 = sxyz[3 * old];
+      y1 = sxyz[3 * old + 1];
+      z1 = sxyz[3 * old + 2];
+    } else {
+      x1 = c[3 * old];
+      y1 = c[3 * old + 1];
+      z1 = c[3 * old + 2];
+    }
+    float best = -1.0f;
+    int bi = 0;
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+      const float d = sqdist3(x[i] - x1, y[i] - y1, z[i] - z1);
+      float d2;  // fminf(d, dist[i]) as the bare instruction (no canonicalising v_max_f32 in front: sampling.hip fps_kernel)
+      asm("v_min_f32 %0, %1, %2" : "=v"(d2) : "v"(d), "v"(dist[i]));
+      dist[i] = d2;
+      if (d2 > best) {
+        best = d2;
+        bi = i;
+      }
+    }
+    // (a thread without points offers the identity, not an index: whatever temp holds, the winner is a point of the cloud)
+    const int bk = t + bi * THREADS;
+    u64 key = pn2_max_u64<true>(bk < n ? pn2_fps_key(best, bk, lt) : 0);
+    if (THREADS > 64) key = pn2_block_max(key, slots, j, t);
+    old = pn2_fps_key_index(key, lt);
+    if (t == 0) out[j] = old;
+  }
+  if (m > 1) {
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+      const int k = t + i * THREADS;
+      if (k < n) tp[k] = dist[i];
+    }
+  }
+}
+
+// n > 16384 (T = 1024): the running minima live in temp, the cloud is streamed from L2 every round
+__global__ __launch_bounds__(1024) void pn2_fps_big_kernel(int n, int m, const float *__restrict__ xyz,
+                                                           float *__restrict__ temp, int *__restrict__ idxs) {
+  __shared__ u64 slots[2 * 16];
+  const int t = threadIdx.x;
+  const float *c = xyz + (size_t)blockIdx.x * 3 * n;
+  float *tp = temp + (size_t)blockIdx.x * n;
+  int *out = idxs + (size_t)blockIdx.x * m;
+  if (t < 32) slots[t] = 0;
+  if (t == 0) out[0] = 0;
+  __syncthreads();
+  int old = 0;
+  for (int j = 1; j < m; ++j) {
+    const float x1 = c[(size_t)3 * old], y1 = c[(size_t)3 * old + 1], z1 = c[(size_t)3 * old + 2];
+    float best = -1.0f;
+    int bk = 0;
+    for (int k = t; k < n; k += 1024) {
+      const float d = sqdist3(c[(size_t)3 * k] - x1, c[(size_t)3 * k + 1] - y1, c[(size_t)3 * k + 2] - z1);
+      const float d2 = fminf(d, tp[k]);
+      tp[k] = d2;
+      if (d2 > best) {
+        best = d2;
+        bk = k;
+      }
+    }
+    const u64 key = pn2_block_max(pn2_max_u64<true>(pn2_fps_key(best, bk, 10)), slots, j, t);
+    old = pn2_fps_key_index(key, 10);
+    if (t == 0) out[j] = old;
+  }
+}
+
+#define PN2_FPS_LDS_MAX (160 * 1024)
+template <int THREADS, int PPT>
+static void pn2_fps_launch(int b, int n, int m, int lt, const float *xyz, float *temp, int *idx, hipStream_t s) {
+  const size_t base = 2 * 16 * sizeof(u64), cloud = (size_t)3 * n * sizeof(float);
+  if (base + cloud <= PN2_FPS_LDS_MAX) {
+    static bool once = false;
+    if (!once) {
+      (void)hipFuncSetAttribute((const void *)pn2_fps_kernel<THREADS, PPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                PN2_FPS_LDS_MAX);
+      once = true;
+    }
+    hipLaunchKernelGGL((pn2_fps_kernel<THREADS, PPT, true>), dim3(b), dim3(THREADS), base + cloud, s, n, m, lt, xyz, temp, idx);
+  } else {
+    hipLaunchKernelGGL((pn2_fps_kernel<THREADS, PPT, false>), dim3(b), dim3(THREADS), base, s, n, m, lt, xyz, temp, idx);
+  }
+}
+
+extern "C" int p2pb_pn2_fps(int b, int n, int m, const float *xyz, float *temp, int *idx, void *stream) {
+  if (b <= 0 || n <= 0 || m < 0) return P2PB_EINVAL;
+  if (m == 0) return 0;  // (PN2/sampling_gpu.cu:108: nothing is written; idx i32[b,0] has no address)
+  if (!xyz || !temp || !idx) return P2PB_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  int lt = 0;  // log2 T(n)
+  while (lt < 10 && (2 << lt) <= n) ++lt;
+  if (n <= 64) pn2_fps_launch<64, 1>(b, n, m, lt, xyz, temp, idx, s);
+  else if (n <= 256) pn2_fps_launch<256, 1>(b, n, m, lt, xyz, temp, idx, s);
+  else if (n <= 1024) pn2_fps_launch<1024, 1>(b, n, m, lt, xyz, temp, idx, s);
+  else if (n <= 2048) pn2_fps_launch<1024, 2>(b, n, m, lt, xyz, temp, idx, s);
+  else if (n <= 4096) pn2_fps_launch<1024, 4>(b, n, m, lt, xyz, temp, idx, s);
+  else if (n <= 8192) pn2_fps_launch<1024, 8>(b, n, m, lt, xyz, temp, idx, s);
+  else if (n <= 16384) pn2_fps_launch<1024, 16>(b, n, m, lt, xyz, temp, idx, s);
+  else hipLaunchKernelGGL(pn2_fps_big_kernel, dim3(b), dim3(1024), 0, s, n, m, xyz, temp, idx);
+  return p2pb_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// three-interpolate: out[b,l,j] = sum_k weight[b,j,k] * features[b,l,idx[b,j,k]], k = 0, 1, 2 left to right in the
+// library's fused form (three_interp_kernel, neighbors.hip). Lanes along n; a thread reads its three (idx, weight)
+// pairs once and walks CC channels, so the writes go out lane-consecutive.
+// The gradient ADDS grad_out * weight_k into grad_features[b,l,idx_k] (global_atomic_add_f32): the caller's buffer is
+// accumulated into, not zeroed (PN2/interpolate_gpu.cu:146-148; the layer passes zeros).
+// ------------------------------------------------------------------------------------------------
+#define PN2_TI_CC 16
+template <bool GRAD>
+__global__ __launch_bounds__(256) void pn2_three_interp_kernel(int c, int m, int n, const float *__restrict__ src,
+                                                               const int *__restrict__ idx,
+                                                               const float *__restrict__ weight, float *dst) {
+  const int b = blockIdx.z;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= n) return;
+  const int *id = idx + ((size_t)b * n + j) * 3;
+  const float *w = weight + ((size_t)b * n + j) * 3;
+  const int a0 = id[0], a1 = id[1], a2 = id[2];
+  const float w0 = w[0], w1 = w[1], w2 = w[2];
+  const int c0 = blockIdx.y * PN2_TI_CC, c1 = min(c0 + PN2_TI_CC, c);
+  for (int l = c0; l < c1; ++l) {
+    if (GRAD) {  // src = grad_out f32[b,c,n], dst = grad_features f32[b,c,m]
+      const float g = src[((size_t)b * c + l) * n + j];
+      float *o = dst + ((size_t)b * c + l) * m;
+      atomicAdd(o + a0, g * w0);
+      atomicAdd(o + a1, g * w1);
+      atomicAdd(o + a2, g * w2);
+    } else {  // src = features f32[b,c,m], dst = out f32[b,c,n]
+      const float *f = src + ((size_t)b * c + l) * m;
+      dst[((size_t)b * c + l) * n + j] = __fmaf_rn(f[a2], w2, __fmaf_rn(f[a1], w1, f[a0] * w0));
+    }
+  }
+}
+
+extern "C" int p2pb_pn2_three_interpolate(int b, int c, int m, int n, const float *features, const int *idx,
+                                          const float *weight, float *out, void *stream) {
+  if (b <= 0 || b > 65535 || c <= 0 || m <= 0 || n <= 0 || !features || !idx || !weight || !out) return P2PB_EINVAL;
+  hipLaunchKernelGGL(pn2_three_interp_kernel<false>, dim3(cdiv(n, 256), cdiv(c, PN2_TI_CC), b), dim3(256), 0,
+                     (hipStream_t)stream, c, m, n, features, idx, weight, out);
+  return p2pb_launch_status();
+}
+
+// Global atomics in an order that is not fixed: refused in deterministic mode, as the library refuses every scatter it
+// cannot run in a fixed order (scatter_grad.hip). The [b,n,3] index layout does not fit that file's LDS-row family.
+extern "C" int p2pb_pn2_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out, const int *idx,
+                                               const float *weight, float *grad_features, void *stream) {
+  if (b <= 0 || b > 65535 || c <= 0 || m <= 0 || n <= 0 || !grad_out || !idx || !weight || !grad_features) return P2PB_EINVAL;
+  if (p2pb_deterministic()) return P2PB_EINVAL;
+  hipLaunchKernelGGL(pn2_three_interp_kernel<true>, dim3(cdiv(n, 256), cdiv(c, PN2_TI_CC), b), dim3(256), 0,
+                     (hipStream_t)stream, c, m, n, grad_out, idx, weight, grad_features);
+  return p2pb_launch_status();
+}

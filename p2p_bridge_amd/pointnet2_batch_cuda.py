@@ -299,3 +299,107 @@ def group_concat(points_coords, centers_coords, points_features, indices):
     call("p2pb_group_concat", _i(b), _i(c), _i(n), _i(m), _i(u), ptr(points_coords), ptr(centers_coords),
          ptr(points_features), ptr(indices), ptr(out), stream_ptr())
     return out
+
+
+# ---- the classic PointNet++ operators (PN2/pointnet2_api.cpp:17-29; csrc/pointnet2_legacy.hip) ----------------------
+# Clouds are POINT-major f32[B,N,3]. The caller allocates every output and passes the sizes as integers, exactly as the
+# reference's layers do (third_party/openpoints/models/layers/{group,subsample,upsampling}.py); the kernels run on the
+# current stream and write into the caller's tensors. The reference's `int` functions return 1, its `void` ones None.
+# Where the reference exit(-1)s on a launch error or reads whatever memory a mismatched argument names, these raise
+# RuntimeError: wrong device, dtype, contiguity, or a shape that disagrees with the integers.
+
+def _pn2_check(*specs):
+    """specs: (tensor, dtype, name, shape). `check` on each, one device for all, shapes equal to what the integers say."""
+    dev = None
+    for t, dtype, name, shape in specs:
+        check(t, dtype, name)
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, the other tensors on {dev}")
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError(f"{name} must have shape {tuple(shape)} for the sizes passed, got {tuple(t.shape)}")
+
+
+def ball_query_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx):
+    """PN2/ball_query.cpp:29. new_xyz f32[B,M,3], xyz f32[B,N,3] -> idx i32[B,M,nsample] (rows without a neighbour are left
+    as they are: the layer zero-fills idx first, group.py:198)"""
+    b, n, m, nsample = int(b), int(n), int(m), int(nsample)
+    _pn2_check((new_xyz, F32, "new_xyz", (b, m, 3)), (xyz, F32, "xyz", (b, n, 3)), (idx, I32, "idx", (b, m, nsample)))
+    call("p2pb_pn2_ball_query", _i(b), _i(n), _i(m), _f(radius), _i(nsample), ptr(new_xyz), ptr(xyz), ptr(idx), stream_ptr())
+    return 1
+
+
+def group_points_wrapper(b, c, n, npoints, nsample, points, idx, out):
+    """PN2/group_points.cpp:25. points f32[B,C,N], idx i32[B,npoints,nsample] -> out f32[B,C,npoints,nsample]"""
+    b, c, n, npoints, nsample = int(b), int(c), int(n), int(npoints), int(nsample)
+    _pn2_check((points, F32, "points", (b, c, n)), (idx, I32, "idx", (b, npoints, nsample)),
+               (out, F32, "out", (b, c, npoints, nsample)))
+    call("p2pb_grouping_forward", _i(b), _i(c), _i(n), _i(npoints), _i(nsample), ptr(points), ptr(idx), ptr(out), stream_ptr())
+    return 1
+
+
+def group_points_grad_wrapper(b, c, n, npoints, nsample, grad_out, idx, grad_points):
+    """PN2/group_points.cpp:13. ADDS the scattered grad_out f32[B,C,npoints,nsample] into grad_points f32[B,C,N]: the
+    library's scatter writes a fresh tensor, which is then added to the caller's."""
+    b, c, n, npoints, nsample = int(b), int(c), int(n), int(npoints), int(nsample)
+    _pn2_check((grad_out, F32, "grad_out", (b, c, npoints, nsample)), (idx, I32, "idx", (b, npoints, nsample)),
+               (grad_points, F32, "grad_points", (b, c, n)))
+    grad_points.add_(grouping_backward(grad_out, idx, n))
+    return 1
+
+
+def gather_points_wrapper(b, c, n, npoints, points, idx, out):
+    """PN2/sampling.cpp:16. points f32[B,C,N], idx i32[B,npoints] -> out f32[B,C,npoints]"""
+    b, c, n, npoints = int(b), int(c), int(n), int(npoints)
+    _pn2_check((points, F32, "points", (b, c, n)), (idx, I32, "idx", (b, npoints)), (out, F32, "out", (b, c, npoints)))
+    call("p2pb_gather_features_forward", _i(b), _i(c), _i(n), _i(npoints), ptr(points), ptr(idx), ptr(out), stream_ptr())
+    return 1
+
+
+def gather_points_grad_wrapper(b, c, n, npoints, grad_out, idx, grad_points):
+    """PN2/sampling.cpp:27. ADDS the scattered grad_out f32[B,C,npoints] into grad_points f32[B,C,N] (as
+    group_points_grad_wrapper)"""
+    b, c, n, npoints = int(b), int(c), int(n), int(npoints)
+    _pn2_check((grad_out, F32, "grad_out", (b, c, npoints)), (idx, I32, "idx", (b, npoints)),
+               (grad_points, F32, "grad_points", (b, c, n)))
+    grad_points.add_(gather_features_backward(grad_out, idx, n))
+    return 1
+
+
+def furthest_point_sampling_wrapper(b, n, m, points, temp, idx):
+    """PN2/sampling.cpp:39. points f32[B,N,3], temp f32[B,N] in/out (the layer fills it with 1e10) -> idx i32[B,m];
+    tie order of the reference's min(2^floor(log2 N), 1024)-thread block (include/p2pb_hip.h p2pb_pn2_fps)"""
+    b, n, m = int(b), int(n), int(m)
+    _pn2_check((points, F32, "points", (b, n, 3)), (temp, F32, "temp", (b, n)), (idx, I32, "idx", (b, max(m, 0))))
+    call("p2pb_pn2_fps", _i(b), _i(n), _i(m), ptr(points), ptr(temp), ptr(idx), stream_ptr())
+    return 1
+
+
+def three_nn_wrapper(b, n, m, unknown, known, dist2, idx):
+    """PN2/interpolate.cpp:20. unknown f32[B,N,3], known f32[B,m,3] -> dist2 f32[B,N,3] (squared), idx i32[B,N,3]"""
+    b, n, m = int(b), int(n), int(m)
+    _pn2_check((unknown, F32, "unknown", (b, n, 3)), (known, F32, "known", (b, m, 3)), (dist2, F32, "dist2", (b, n, 3)),
+               (idx, I32, "idx", (b, n, 3)))
+    call("p2pb_pn2_three_nn", _i(b), _i(n), _i(m), ptr(unknown), ptr(known), ptr(dist2), ptr(idx), stream_ptr())
+
+
+def three_interpolate_wrapper(b, c, m, n, points, idx, weight, out):
+    """PN2/interpolate.cpp:31. points f32[B,c,m], idx i32[B,n,3], weight f32[B,n,3] -> out f32[B,c,n]"""
+    b, c, m, n = int(b), int(c), int(m), int(n)
+    _pn2_check((points, F32, "points", (b, c, m)), (idx, I32, "idx", (b, n, 3)), (weight, F32, "weight", (b, n, 3)),
+               (out, F32, "out", (b, c, n)))
+    call("p2pb_pn2_three_interpolate", _i(b), _i(c), _i(m), _i(n), ptr(points), ptr(idx), ptr(weight), ptr(out), stream_ptr())
+
+
+def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_points):
+    """PN2/interpolate.cpp:45. ADDS grad_out f32[B,c,n] * weight at idx into grad_points f32[B,c,m] (fp32 atomics in no
+    fixed order: refused inside p2p_bridge_amd.deterministic())"""
+    b, c, n, m = int(b), int(c), int(n), int(m)
+    _pn2_check((grad_out, F32, "grad_out", (b, c, n)), (idx, I32, "idx", (b, n, 3)), (weight, F32, "weight", (b, n, 3)),
+               (grad_points, F32, "grad_points", (b, c, m)))
+    if lib().p2pb_get_deterministic():
+        raise P2PBError("three_interpolate_grad_wrapper: no deterministic kernel (it accumulates with fp32 atomics, whose order is "
+                        "not fixed): run this backward pass outside p2p_bridge_amd.deterministic()")
+    call("p2pb_pn2_three_interpolate_grad", _i(b), _i(c), _i(n), _i(m), ptr(grad_out), ptr(idx), ptr(weight), ptr(grad_points),
+         stream_ptr())
