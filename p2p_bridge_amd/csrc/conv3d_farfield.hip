@@ -96,8 +96,29 @@ static __global__ __launch_bounds__(1024) void far_field_kernel(int cin, int cou
     float acc = 0.0f;
     if (co < cout) {
       const float4 *w4 = (const float4 *)wt + ((size_t)tap * nchunk * 2) * cout_pad + co;
-#pragma unroll 4
-      for (int k8 = 0; k8 < nchunk; ++k8) {
+      // Whole chunks four at a time, their eight weight loads issued together: with the ragged-chunk tests inside the loop every
+      // chunk's two loads were waited for (vmcnt(0)) before the next chunk's were issued, one L2 round trip per eight input
+      // channels (profiles/r07_gather_wait_audit.txt). Same fused multiply-adds in the same ascending input-channel order.
+      int k8 = 0;
+      for (; k8 + 4 <= cin / 8; k8 += 4) {
+        float4 h[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) h[q] = w4[(size_t)(2 * k8 + q) * cout_pad];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 h0 = h[2 * q], h1 = h[2 * q + 1];
+          const float *av = a + (k8 + q) * 8;
+          acc = __fmaf_rn(h0.x, av[0], acc);
+          acc = __fmaf_rn(h1.x, av[1], acc);
+          acc = __fmaf_rn(h0.y, av[2], acc);
+          acc = __fmaf_rn(h1.y, av[3], acc);
+          acc = __fmaf_rn(h0.z, av[4], acc);
+          acc = __fmaf_rn(h1.z, av[5], acc);
+          acc = __fmaf_rn(h0.w, av[6], acc);
+          acc = __fmaf_rn(h1.w, av[7], acc);
+        }
+      }
+      for (; k8 < nchunk; ++k8) {
         const float4 h0 = w4[(size_t)(2 * k8) * cout_pad], h1 = w4[(size_t)(2 * k8 + 1) * cout_pad];
         const float *av = a + k8 * 8;
         const int left = cin - k8 * 8;  // (a ragged last chunk: the channels that exist, in order)

@@ -244,16 +244,34 @@ __global__ __launch_bounds__(256) void group_sub_kernel(int c, int n, int m, int
   {
     const int c0 = blockIdx.y * cpl;  // one channel chunk per workgroup (more workgroups on the small levels)
     const int ch = c0 + chl;
-#pragma unroll 4
-    for (int it = 0; it < 16 / pps; ++it) {
-      const int pl = wave * 16 + it * pps + sub;
-      const int id = __shfl(id_mine, it * pps + sub);
-      float v = 0.0f;
-      if (id >= 0 && ch < c) {
-        v = zt[((size_t)b * n + id) * c + ch];
-        if (cxt) v -= cxt[((size_t)b * m + (p0 + pl) / u) * c + ch];
+    // Loads are issued eight steps at a time, from clamped addresses, and the masking is a select afterwards: a load inside a
+    // per-step branch is waited for (vmcnt(0)) before the next step issues its own, one L2 round trip per step
+    // (profiles/r07_gather_wait_audit.txt). The centre index is advanced, not divided out per step.
+    const float *zb = zt + (size_t)b * n * c + min(ch, c - 1);
+    const float *cb = cxt ? cxt + (size_t)b * m * c + min(ch, c - 1) : nullptr;
+    int cj = (p0 + wave * 16 + sub) / u, cr = (p0 + wave * 16 + sub) - cj * u;  // centre of the lane's first position, offset in it
+    for (int it0 = 0; it0 < 16 / pps; it0 += 8) {
+      int id[8];
+      float zv[8], cv[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        id[k] = __shfl(id_mine, (it0 + k) * pps + sub);
+        zv[k] = zb[(size_t)max(id[k], 0) * c];
+        cv[k] = cb ? cb[(size_t)min(cj, m - 1) * c] : 0.0f;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+          const bool wrap = q < pps && cr + 1 == u;
+          cr = wrap ? 0 : (q < pps ? cr + 1 : cr);
+          cj += wrap ? 1 : 0;
+        }
       }
-      tile[chl][pl] = v;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int pl = wave * 16 + (it0 + k) * pps + sub;
+        float v = zv[k];
+        if (cb) v -= cv[k];
+        tile[chl][pl] = (id[k] >= 0 && ch < c) ? v : 0.0f;
+      }
     }
     __syncthreads();
     const int pt = lane;
@@ -286,7 +304,13 @@ __global__ __launch_bounds__(256) void group_sub_kernel(int c, int n, int m, int
 // (two positions per step for c <= 32: the half-waves' sums are added once at the end). Slots of 128 positions: a quarter of the
 // partials gn_affine has to reduce afterwards.
 #define GST_PW 128
-template <int CPL>
+// Round 7: the loads of GST_NB steps are issued together, from clamped addresses, and the masking is a select on the two sums
+// afterwards (same additions, same order): with `if (id >= 0 && chok) { load; load; add }` per step every step sat in its own
+// exec-masked branch and its loads were waited for (vmcnt(0)) before the next step issued any -- a wave walked its slot as 64 or
+// 128 dependent L2 round trips (profiles/r07_gather_wait_audit.txt). The neighbour index comes by v_readlane (uniform lane
+// number: a scalar row base for c > 32) instead of ds_bpermute, the centre index is advanced instead of divided out per step.
+#define GST_NB 16
+template <int CPL, bool CX>
 __global__ __launch_bounds__(256) void group_stats_kernel(int c, int n, int m, int u, int nslots, const float *__restrict__ zt,
                                                           const float *__restrict__ cxt, const int *__restrict__ idx,
                                                           float *__restrict__ stats) {
@@ -296,22 +320,43 @@ __global__ __launch_bounds__(256) void group_stats_kernel(int c, int n, int m, i
   if (slot >= nslots) return;
   const int mu = m * u, p0 = slot * GST_PW;
   const int sub = lane / CPL, ch = blockIdx.y * CPL + lane % CPL;
-  // the wave's 128 neighbour indices: two per lane, handed round by lane broadcasts
+  // the wave's 128 neighbour indices: two per lane, handed round by lane reads
   const int ia = p0 + lane < mu ? idx[(size_t)b * mu + p0 + lane] : -1;
   const int ib = p0 + 64 + lane < mu ? idx[(size_t)b * mu + p0 + 64 + lane] : -1;
-  const float *zb = zt + (size_t)b * n * c + ch;
-  const float *cb = cxt ? cxt + (size_t)b * m * c + ch : nullptr;
-  float s1 = 0.0f, s2 = 0.0f;
   const bool chok = ch < c;
-#pragma unroll 8
-  for (int it = 0; it < GST_PW / PPS; ++it) {
-    const int pl = it * PPS + sub;
-    const int id = pl < 64 ? __shfl(ia, pl) : __shfl(ib, pl - 64);
-    if (id >= 0 && chok) {
-      float v = zb[(size_t)id * c];
-      if (cb) v -= cb[(size_t)((p0 + pl) / u) * c];
-      s1 += v;
-      s2 += v * v;
+  const float *zb = zt + (size_t)b * n * c + min(ch, c - 1);
+  const float *cb = CX ? cxt + (size_t)b * m * c + min(ch, c - 1) : nullptr;
+  int cj = (p0 + sub) / u, cr = (p0 + sub) - cj * u;  // centre of the lane's first position, offset inside its neighbourhood
+  float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll 1
+  for (int pb = 0; pb < GST_PW; pb += GST_NB * PPS) {  // (a batch lies in one half of the slot: ia or ib)
+    const int src = pb < 64 ? ia : ib;
+    int id[GST_NB];
+    float zv[GST_NB], cv[GST_NB];
+#pragma unroll
+    for (int k = 0; k < GST_NB; ++k) {
+      const int l = (pb & 63) + k * PPS;
+      id[k] = __builtin_amdgcn_readlane(src, l);
+      if (PPS == 2) id[k] = sub ? __builtin_amdgcn_readlane(src, l + 1) : id[k];
+      zv[k] = zb[(size_t)max(id[k], 0) * c];
+      if (CX) {
+        cv[k] = cb[(size_t)min(cj, m - 1) * c];
+#pragma unroll
+        for (int q = 0; q < PPS; ++q) {
+          const bool wrap = cr + 1 == u;
+          cr = wrap ? 0 : cr + 1;
+          cj += wrap ? 1 : 0;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < GST_NB; ++k) {  // ascending positions: the chain every lane has always run
+      float v = zv[k];
+      if (CX) v -= cv[k];
+      const bool ok = id[k] >= 0 && chok;
+      const float t1 = s1 + v, t2 = s2 + v * v;
+      s1 = ok ? t1 : s1;
+      s2 = ok ? t2 : s2;
     }
   }
   if (PPS == 2) {
@@ -325,6 +370,14 @@ __global__ __launch_bounds__(256) void group_stats_kernel(int c, int n, int m, i
   }
 }
 
+template <int CPL>
+static void group_stats_launch(int b, int c, int n, int m, int u, int nslots, const float *zt, const float *cxt, const int *idx,
+                               float *stats_part, hipStream_t s) {
+  const dim3 grid(cdiv(nslots, 4), cdiv(c, CPL), b);
+  if (cxt) hipLaunchKernelGGL((group_stats_kernel<CPL, true>), grid, dim3(256), 0, s, c, n, m, u, nslots, zt, cxt, idx, stats_part);
+  else hipLaunchKernelGGL((group_stats_kernel<CPL, false>), grid, dim3(256), 0, s, c, n, m, u, nslots, zt, cxt, idx, stats_part);
+}
+
 extern "C" int p2pb_group_sub_stats_slots(int m, int u) { return (int)(((long)m * u + GST_PW - 1) / GST_PW); }
 // zt f32[b,n,c], cxt f32[b,m,c] | NULL (point-major), idx i32[b,m,u] -> stats_part f32[b, p2pb_group_sub_stats_slots(m,u), c, 2]
 extern "C" int p2pb_group_sub_stats(int b, int c, int n, int m, int u, const float *zt, const float *cxt, const int *idx,
@@ -332,12 +385,8 @@ extern "C" int p2pb_group_sub_stats(int b, int c, int n, int m, int u, const flo
   if (b <= 0 || c <= 0 || n <= 0 || m <= 0 || u <= 0 || !zt || !idx || !stats_part || (long)m * u > 0x7fffffffL) return P2PB_EINVAL;
   const int nslots = p2pb_group_sub_stats_slots(m, u);
   hipStream_t s = (hipStream_t)stream;
-  if (c <= 32)
-    hipLaunchKernelGGL(group_stats_kernel<32>, dim3(cdiv(nslots, 4), cdiv(c, 32), b), dim3(256), 0, s, c, n, m, u, nslots, zt, cxt, idx,
-                       stats_part);
-  else
-    hipLaunchKernelGGL(group_stats_kernel<64>, dim3(cdiv(nslots, 4), cdiv(c, 64), b), dim3(256), 0, s, c, n, m, u, nslots, zt, cxt, idx,
-                       stats_part);
+  if (c <= 32) group_stats_launch<32>(b, c, n, m, u, nslots, zt, cxt, idx, stats_part, s);
+  else group_stats_launch<64>(b, c, n, m, u, nslots, zt, cxt, idx, stats_part, s);
   return p2pb_launch_status();
 }
 
@@ -781,26 +830,43 @@ __global__ __launch_bounds__(256) void three_interp_add_kernel(int c, int m, int
     const int ch = c0 + lane;
     if (ch < c) {
       const float *f = czt + (size_t)b * m * c + ch;  // point-major coarse features: one contiguous row per neighbour
-#pragma unroll 4
-      for (int pl = wave * 16; pl < wave * 16 + 16; ++pl)
-        tile[lane][pl] = __fmaf_rn(f[(size_t)sid[pl][2] * c], sw[pl][2],
-                                   __fmaf_rn(f[(size_t)sid[pl][1] * c], sw[pl][1], f[(size_t)sid[pl][0] * c] * sw[pl][0]));
+      // (eight positions' rows per batch: left to the unroller, two positions' six loads were waited for together, eight round
+      // trips for the wave's sixteen positions)
+      for (int pl0 = wave * 16; pl0 < wave * 16 + 16; pl0 += 8) {
+        float g[8][3];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) g[k][q] = f[(size_t)sid[pl0 + k][q] * c];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          tile[lane][pl0 + k] = __fmaf_rn(g[k][2], sw[pl0 + k][2], __fmaf_rn(g[k][1], sw[pl0 + k][1], g[k][0] * sw[pl0 + k][0]));
+      }
     }
-    __syncthreads();
     const int pt = lane;
     const bool pok = p0 + pt < n;
+    // The `add` and `bias` values of the thread's 16 rows are loaded here, all at once and from clamped addresses (rows >= c,
+    // positions >= n), while the waves meet at the barrier: loaded inside the row loop's branches each was waited for
+    // (vmcnt(0)) before the next was issued, 32 L2 round trips in a row (profiles/r07_gather_wait_audit.txt).
+    float av[16], bv[16];
+    if (add) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) av[k] = add[((size_t)b * c + min(c0 + wave + 4 * k, c - 1)) * n + min(p0 + pt, n - 1)];
+    }
+    if (bias) {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) bv[k] = bias[min(c0 + wave + 4 * k, c - 1)];
+    }
+    __syncthreads();
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       const int cr = wave + 4 * k;  // (see group_sub_kernel)
       if (c0 + cr < c) {
-        float v = 0.0f;
-        if (pok) {
-          const size_t o = ((size_t)b * c + c0 + cr) * n + p0 + pt;
-          v = tile[cr][pt];
-          if (add) v += add[o];
-          if (bias) v += bias[c0 + cr];
-          out[o] = v;
-        }
+        float v = tile[cr][pt];
+        if (add) v += av[k];
+        if (bias) v += bv[k];
+        v = pok ? v : 0.0f;
+        if (pok) out[((size_t)b * c + c0 + cr) * n + p0 + pt] = v;
         const float s1 = halfwave_sum_to_last(v), s2 = halfwave_sum_to_last(v * v);
         if ((lane & 31) == 31) {
           float *p = stats + (((size_t)b * nslots + blockIdx.x * 2 + (lane >> 5)) * c + c0 + cr) * 2;

@@ -62,7 +62,19 @@ __device__ __forceinline__ void se_hidden(int c, int hidden, const float *__rest
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   for (int h = wave; h < hidden; h += nw) {
     float acc = 0.0f;
-    for (int i = lane; i < c; i += 64) acc = __fmaf_rn(w1[(size_t)h * c + i], mean[i], acc);
+    // (a lane's terms eight at a time, the weight loads issued together from clamped addresses and the tail masked by a select:
+    // term by term every load was waited for before the next was issued; profiles/r07_gather_wait_audit.txt. Same order.)
+    for (int i0 = lane; i0 < c; i0 += 64 * 8) {
+      float wv[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) wv[q] = w1[(size_t)h * c + min(i0 + 64 * q, c - 1)];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int i = i0 + 64 * q;
+        const float t = __fmaf_rn(wv[q], mean[min(i, c - 1)], acc);
+        acc = i < c ? t : acc;
+      }
+    }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
     if (lane == 0) hid[h] = fmaxf(acc, 0.0f);

@@ -417,21 +417,37 @@ __global__ __launch_bounds__(256) void vox_gather_cl_split_kernel(int c, int nch
     const int *seg = slist + (size_t)b * n + (cur[(size_t)b * r3 + v] - cn);
     const float div = (float)(1.0 / (double)(float)cn);  // PN2/vox_gpu.cu:70 divides a double literal
     const float *f = feat_t + (size_t)b * n * c + ch;
-    for (int q = 0; q < cn; ++q) {
-      const float *fq = f + (size_t)seg[q] * c;
-      if (ALIGNED) {
+    // the list entries and rows of FOUR points in flight before the first is added, as in vox_gather_cl_occ_split_kernel below:
+    // point by point every point was two dependent L2 round trips (list entry -> row; profiles/r07_gather_wait_audit.txt).
+    // The additions keep their order.
+    for (int q0 = 0; q0 < cn; q0 += 4) {
+      int id[4];
 #pragma unroll
-        for (int h = 0; h < 2; ++h)
-          if (ch + 4 * h < c) {
-            const vox_f32x4 x = *(const vox_f32x4 *)(fq + 4 * h);
+      for (int u = 0; u < 4; ++u) id[u] = seg[min(q0 + u, cn - 1)];
+      float x[4][8];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[4 * h + i] += x[i] * div;
+      for (int u = 0; u < 4; ++u) {
+        const float *fq = f + (size_t)id[u] * c;
+        if (ALIGNED) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            vox_f32x4 y = vox_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+            if (ch + 4 * h < c) y = *(const vox_f32x4 *)(fq + 4 * h);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) x[u][4 * h + i] = y[i];
           }
-      } else {
+        } else {
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
-          if (ch + i < c) acc[i] += fq[i] * div;
+          for (int i = 0; i < 8; ++i) x[u][i] = ch + i < c ? fq[i] : 0.0f;
+        }
       }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (q0 + u < cn) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            if (ch + (ALIGNED ? i & 4 : i) < c) acc[i] += x[u][i] * div;
+        }
     }
   }
   u32x4 p0, p1;
@@ -782,23 +798,44 @@ __global__ __launch_bounds__(256) void devox_cl_kernel(int c, int n, int r, cons
     const int ch = c0 + lane;
     if (ch < c) {
       const float a = aff_a ? aff_a[(size_t)b * c + ch] : 1.0f, bb = aff_b ? aff_b[(size_t)b * c + ch] : 0.0f;
-#pragma unroll 2
-      for (int pl = wave * 16; pl < wave * 16 + 16; ++pl) {
-        float fv[8];
+      // (the corner rows of two points per batch: left to the unroller, one point's eight loads were waited for before the next
+      // point's were issued, sixteen round trips for the wave's sixteen points)
+      for (int pl0 = wave * 16; pl0 < wave * 16 + 16; pl0 += 2) {
+        float fv[2][8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) fv[q] = g[(size_t)sidx[pl][q] * c + ch];
-        if (aff_a) {
+        for (int u = 0; u < 2; ++u)
 #pragma unroll
-          for (int q = 0; q < 8; ++q) fv[q] = fv[q] * a + bb;
+          for (int q = 0; q < 8; ++q) fv[u][q] = g[(size_t)sidx[pl0 + u][q] * c + ch];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int pl = pl0 + u;
+          if (aff_a) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) fv[u][q] = fv[u][q] * a + bb;
+          }
+          float acc = sw[pl][0] * fv[u][0];
+#pragma unroll
+          for (int q = 1; q < 8; ++q) acc = __fmaf_rn(sw[pl][q], fv[u][q], acc);
+          tile[lane][pl] = acc;
         }
-        float acc = sw[pl][0] * fv[0];
+      }
+    }
+    const int pt = t & 63;
+    // The point branch's values for the thread's 16 rows (`add`, and the row's scale / shift) are loaded here, all at once and from
+    // clamped addresses (rows >= c, points >= n), while the waves meet at the barrier: loaded inside the write-back loop each
+    // row's three were waited for (vmcnt(0)) before the next row's were issued, sixteen L2 round trips behind the LDS transpose
+    // (profiles/r07_gather_wait_audit.txt).
+    float hv[16], hsc[16], hsh[16];
+    if (add) {
 #pragma unroll
-        for (int q = 1; q < 8; ++q) acc = __fmaf_rn(sw[pl][q], fv[q], acc);
-        tile[lane][pl] = acc;
+      for (int k = 0; k < 16; ++k) {
+        const size_t row = (size_t)b * c + min(c0 + (t >> 6) + 4 * k, c - 1);
+        hv[k] = add[row * n + min(p0 + pt, n - 1)];
+        hsc[k] = add_scale[row];
+        hsh[k] = add_shift[row];
       }
     }
     __syncthreads();
-    const int pt = t & 63;
     if (p0 + pt < n) {
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
@@ -807,7 +844,7 @@ __global__ __launch_bounds__(256) void devox_cl_kernel(int c, int n, int r, cons
           const size_t o = ((size_t)b * c + c0 + cr) * n + p0 + pt;
           float v = tile[cr][pt];
           if (add) {
-            const float z = add[o] * add_scale[(size_t)b * c + c0 + cr] + add_shift[(size_t)b * c + c0 + cr];
+            const float z = hv[k] * hsc[k] + hsh[k];
             v = z * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.44269504088896340736f)) + v;
           }
           outs[o] = v;
@@ -878,8 +915,20 @@ __global__ __launch_bounds__(256) void devox_cl4_kernel(int c, int n, int r, con
       }
     }
   }
-  __syncthreads();
   const int pt = t & 63;
+  // the point branch's values of the thread's 16 rows, loaded at once from clamped addresses while the waves meet at the barrier
+  // (see devox_cl_kernel; profiles/r07_gather_wait_audit.txt)
+  float hv[16], hsc[16], hsh[16];
+  if (add) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const size_t row = (size_t)b * c + c0 + (t >> 6) + 4 * k;
+      hv[k] = add[row * n + min(p0 + pt, n - 1)];
+      hsc[k] = add_scale[row];
+      hsh[k] = add_shift[row];
+    }
+  }
+  __syncthreads();
   if (p0 + pt < n) {
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
@@ -887,7 +936,7 @@ __global__ __launch_bounds__(256) void devox_cl4_kernel(int c, int n, int r, con
       const size_t o = ((size_t)b * c + c0 + cr) * n + p0 + pt;
       float v = tile[cr][pt];
       if (add) {
-        const float z = add[o] * add_scale[(size_t)b * c + c0 + cr] + add_shift[(size_t)b * c + c0 + cr];
+        const float z = hv[k] * hsc[k] + hsh[k];
         v = z * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.44269504088896340736f)) + v;
       }
       outs[o] = v;
