@@ -30,8 +30,8 @@ extern "C" {
 
 #define P2PB_EINVAL (-22)
 
-/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (11: the five
- * p2pb_pn2_* operators added; 10: the GroupNorm finisher is
+/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (12: the eleven
+ * p2pb_pointops_* operators added; 11: the five p2pb_pn2_* operators added; 10: the GroupNorm finisher is
  * passed to p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather as fin_* arguments, the three
  * entry points that armed one for the thread's next launch removed; 9: the set metrics
  * p2pb_pairwise_chamfer / p2pb_pairwise_emd / p2pb_occupancy_* added; 8: p2pb_softmax_attention_* added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
@@ -39,7 +39,7 @@ extern "C" {
  * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
  * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
-#define P2PB_ABI_VERSION 11
+#define P2PB_ABI_VERSION 12
 
 /* library / device info --------------------------------------------------------------------- */
 int p2pb_version(void);            /* == P2PB_ABI_VERSION of the header the library was built from */
@@ -231,6 +231,81 @@ int p2pb_pn2_three_interpolate(int b, int c, int m, int n, const float *features
                                float *out, void *stream);
 int p2pb_pn2_three_interpolate_grad(int b, int c, int n, int m, const float *grad_out, const int *idx, const float *weight,
                                     float *grad_features, void *stream);
+
+/* ---- the packed-batch ("offset") operators of the reference's pointops extension (csrc/pointops.hip) --------------------
+ * Replace the launchers behind third_party/openpoints/cpp/pointops/src/pointops_api.cpp:15-25 (PO = that src directory).
+ * A batch is ONE packed cloud xyz f32[n,3] with cumulative ends offset i32[b]: segment s holds the points
+ * [offset[s-1], offset[s]), offset[-1] = 0; queries new_xyz f32[m,3] are packed the same way by new_offset i32[b]. Features
+ * are POINT-major f32[n,c]. THE CALLER ALLOCATES AND INITIALISES EVERY OUTPUT, as the reference's layer does
+ * (PO/../functions/pointops.py). A size of 0 (m, c, nsample of the arithmetic kernels, ...) returns 0 without a launch; a
+ * negative size or a NULL operand is P2PB_EINVAL. Squared distances: fma(dz,dz, fma(dy,dy, dx*dx)), d = query - point.
+ * Segment lookup: query i belongs to the first segment s with i < new_offset[s], found by a search over b entries that ends
+ * in [0, b-1] whatever the array holds (a query past new_offset[b-1] falls to the last segment); segment ends are clamped
+ * to [0, n] and an end below its start is an empty segment. Offsets holding garbage therefore give no out-of-range access
+ * and no index outside [0, n) (PO/knnquery/knnquery_cuda_kernel.cu:6 get_bt_idx has no such bound).
+ * The kernels that CONSUME an idx trust its values, as the reference and p2pb_grouping_forward do.
+ *
+ * p2pb_pointops_knnquery (PO/knnquery/knnquery_cuda_kernel.cu:65): idx i32[m,nsample], dist2 f32[m,nsample] = the nsample
+ *   smallest squared distances of the query's segment, ascending, with GLOBAL point indices. EQUAL DISTANCES: ASCENDING POINT
+ *   INDEX (a deliberate deviation: the reference's order among equals is whatever its heap leaves). Slots start as
+ *   (1e10, segment start) and admission is strict '<', so a segment with fewer than nsample points leaves its trailing slots
+ *   at dist2 = 1e10, idx = segment start (min(start, n-1) for an empty segment at the very end), as in the reference.
+ *   1 <= nsample <= 100, else P2PB_EINVAL (the reference overruns its 100-entry arrays above that).
+ * p2pb_pointops_ballquery (PO/ballquery/ballquery_cuda_kernel.cu:26): idx i32[m,nsample] = the first nsample points of the
+ *   segment in ascending index with d2 < radius*radius (float product, strict); the first hit fills every slot, later hits
+ *   overwrite slots 1, 2, ... A QUERY WITHOUT A HIT LEAVES ITS ROW UNTOUCHED (p2pb_pn2_ball_query's contract, with segments
+ *   and global indices). nsample >= 1.
+ * p2pb_pointops_furthestsampling (PO/sampling/sampling_cuda_kernel.cu:15): tmp f32[n] IN/OUT (running minima by GLOBAL point
+ *   index; the layer fills it with 1e10) -> idx i32[m], m = new_offset[b-1] (passed so that the kernel holds to the buffer:
+ *   sample ranges are clamped to [0, m]). Per segment idx[start_m] = start_n; each later sample does
+ *   tmp[k] = min(tmp[k], d2(k, last)) over the segment and takes the maximum of tmp in the order (tmp desc,
+ *   (k - start_n) mod T asc, k asc), T = min(2^floor(log2 n_max), 1024): the reference's block size (PO/cuda_utils.h:11-15)
+ *   and its lower-thread-wins tree. T COMES FROM n_max, THE LONGEST SEGMENT, AND IS THE SAME FOR EVERY SEGMENT. A segment with
+ *   no samples, or with no points, writes nothing (the reference writes idx[start_m] even then); one that asks for more
+ *   samples than it has points repeats indices. One workgroup per segment: minima in registers for segments up to 16384
+ *   points (and up to what n_max announced), else tmp itself is the working array.
+ * p2pb_pointops_grouping_forward (PO/grouping/grouping_cuda_kernel.cu:27): output f32[m,nsample,c] = input f32[n,c] at idx.
+ * p2pb_pointops_grouping_backward (:34): grad_input f32[n,c] += grad_output f32[m,nsample,c] at idx.
+ * p2pb_pointops_interpolation_forward (PO/interpolation/interpolation_cuda_kernel.cu:35): input f32[m,c], idx i32[n,k],
+ *   weight f32[n,k]: acc = output[.]; for i < k: acc = fma(input[idx_i], w_i, acc); output f32[n,c] = acc -- it ADDS TO WHAT
+ *   THE CALLER PASSED (the reference's +=; the layer passes zeros).
+ * p2pb_pointops_interpolation_backward (:42): grad_input f32[m,c] at idx_i += grad_output * w_i.
+ * p2pb_pointops_subtraction_forward (PO/subtraction/subtraction_cuda_kernel.cu:32): output f32[n,nsample,c] =
+ *   input1[n] - input2[idx] (written).
+ * p2pb_pointops_subtraction_backward (:39): grad_input1[n] += grad_output[n,s] for s ascending (a row sum, no atomics);
+ *   grad_input2[idx] += -grad_output.
+ * p2pb_pointops_aggregation_forward (PO/aggregation/aggregation_cuda_kernel.cu:41): acc = output[.]; for s ascending:
+ *   acc = fma(input[idx_s, ch] + position[n,s,ch], weight[n,s, ch mod w_c], acc); output f32[n,c] = acc. c % w_c == 0, else
+ *   P2PB_EINVAL.
+ * p2pb_pointops_aggregation_backward (:48): grad_input[idx_s, ch] += g w; grad_position[n,s,ch] = g w (WRITTEN);
+ *   grad_weight[n,s,j] += g (input + position) over the channels ch = j (mod w_c) in ascending ch (one thread per (n,s,j),
+ *   no atomics).
+ * The four scatter-adds (grad_input of grouping, interpolation and aggregation, grad_input2 of subtraction) are fp32 global
+ * atomics in no fixed order: in deterministic mode (p2pb_set_deterministic) those four entry points return P2PB_EINVAL
+ * before anything is launched, like p2pb_pn2_three_interpolate_grad. subtraction_backward and aggregation_backward accept
+ * NULL for that one target and then run only their fixed-order parts, in either mode. */
+int p2pb_pointops_knnquery(int b, int n, int m, int nsample, const float *xyz, const float *new_xyz, const int *offset,
+                           const int *new_offset, int *idx, float *dist2, void *stream);
+int p2pb_pointops_ballquery(int b, int n, int m, float radius, int nsample, const float *xyz, const float *new_xyz,
+                            const int *offset, const int *new_offset, int *idx, void *stream);
+int p2pb_pointops_furthestsampling(int b, int n, int m, int n_max, const float *xyz, const int *offset, const int *new_offset,
+                                   float *tmp, int *idx, void *stream);
+int p2pb_pointops_grouping_forward(int m, int nsample, int c, const float *input, const int *idx, float *output, void *stream);
+int p2pb_pointops_grouping_backward(int n, int m, int nsample, int c, const float *grad_output, const int *idx,
+                                    float *grad_input, void *stream);
+int p2pb_pointops_interpolation_forward(int n, int c, int k, const float *input, const int *idx, const float *weight,
+                                        float *output, void *stream);
+int p2pb_pointops_interpolation_backward(int n, int c, int k, const float *grad_output, const int *idx, const float *weight,
+                                         float *grad_input, void *stream);
+int p2pb_pointops_subtraction_forward(int n, int nsample, int c, const float *input1, const float *input2, const int *idx,
+                                      float *output, void *stream);
+int p2pb_pointops_subtraction_backward(int n, int nsample, int c, const int *idx, const float *grad_output, float *grad_input1,
+                                       float *grad_input2, void *stream);
+int p2pb_pointops_aggregation_forward(int n, int nsample, int c, int w_c, const float *input, const float *position,
+                                      const float *weight, const int *idx, float *output, void *stream);
+int p2pb_pointops_aggregation_backward(int n, int nsample, int c, int w_c, const float *input, const float *position,
+                                       const float *weight, const int *idx, const float *grad_output, float *grad_input,
+                                       float *grad_position, float *grad_weight, void *stream);
 
 /* chamfer_3D: replaces chamfer_cuda_forward/backward (metrics/chamfer3D/chamfer3D.cu:135,176;
  * kernels :12,:155). xyz are POINT-major f32[b,n,3] / f32[b,m,3]. Lowest index wins distance ties.

@@ -3,7 +3,8 @@
 Layout (DESIGN.md):
   csrc/                     hand-written HIP kernels + the C ABI (include/p2pb_hip.h) -> libp2pb_hip.so
   pointnet2_batch_cuda.py   drop-in for the reference's extension module of the same name
-  metric_modules.py         drop-ins for chamfer_3D / emd_cuda / emd_assignment
+  pointops_cuda.py          drop-in for the reference's packed-batch extension of the same name; pointops.py: its layer API
+  metric_modules.py         drop-ins for chamfer_3D / emd_cuda / emd_assignment / chamfer
   layers.py                 the reference's autograd wrappers (openpoints/models/layers/*) on those
   ... network / sampler mirror of models/{pvcnn,unet_pvc,p2pb}.py
 
@@ -48,13 +49,17 @@ def install_dropin():
     """Register the drop-in modules under the names the reference's Python imports, so that
     `import pointnet2_batch_cuda` (third_party/openpoints/cpp/pointnet2_batch/__init__.py:1),
     `_pvcnn_backend`, `chamfer_3D` (metrics/chamfer3D/dist_chamfer_3D.py:11), `emd_cuda`
-    (metrics/PyTorchEMD/emd.py:1) and `emd_assignment` (metrics/emd_assignment/emd_module.py:24)
-    resolve to the gfx950 implementation."""
-    from . import metric_modules, pointnet2_batch_cuda
+    (metrics/PyTorchEMD/emd.py:1), `emd_assignment` (metrics/emd_assignment/emd_module.py:24), `pointops_cuda`
+    (third_party/openpoints/cpp/pointops/functions/pointops.py:1) and `chamfer`
+    (third_party/openpoints/cpp/chamfer_dist/__init__.py:8) resolve to the gfx950 implementation: all seven extension
+    modules the reference's installer builds."""
+    from . import metric_modules, pointnet2_batch_cuda, pointops_cuda
 
     sys.modules["pointnet2_batch_cuda"] = pointnet2_batch_cuda
     sys.modules["_pvcnn_backend"] = pointnet2_batch_cuda
     sys.modules["chamfer_3D"] = metric_modules.chamfer_3D
     sys.modules["emd_cuda"] = metric_modules.emd_cuda
     sys.modules["emd_assignment"] = metric_modules.emd_assignment
+    sys.modules["pointops_cuda"] = pointops_cuda.module
+    sys.modules["chamfer"] = metric_modules.chamfer
     return pointnet2_batch_cuda

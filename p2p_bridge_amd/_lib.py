@@ -38,9 +38,13 @@ SYMBOLS = [
     "p2pb_pairwise_chamfer_ws_bytes", "p2pb_pairwise_chamfer", "p2pb_pairwise_emd_ws_bytes", "p2pb_pairwise_emd",
     "p2pb_occupancy_grid_cells", "p2pb_occupancy_ws_bytes", "p2pb_occupancy_counts",
     "p2pb_pn2_ball_query", "p2pb_pn2_three_nn", "p2pb_pn2_fps", "p2pb_pn2_three_interpolate", "p2pb_pn2_three_interpolate_grad",
+    "p2pb_pointops_knnquery", "p2pb_pointops_ballquery", "p2pb_pointops_furthestsampling", "p2pb_pointops_grouping_forward",
+    "p2pb_pointops_grouping_backward", "p2pb_pointops_interpolation_forward", "p2pb_pointops_interpolation_backward",
+    "p2pb_pointops_subtraction_forward", "p2pb_pointops_subtraction_backward", "p2pb_pointops_aggregation_forward",
+    "p2pb_pointops_aggregation_backward",
 ]
 
-ABI_VERSION = 11  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
+ABI_VERSION = 12  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
 
 _lib = None
 

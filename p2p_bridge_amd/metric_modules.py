@@ -1,6 +1,7 @@
-"""Drop-ins for the reference's three metric extension modules, on the gfx950 C-ABI library:
+"""Drop-ins for the reference's metric extension modules, on the gfx950 C-ABI library:
 
   chamfer_3D      forward/backward                       (metrics/chamfer3D/chamfer_cuda.cpp:17-32)
+  chamfer         forward/backward                       (third_party/openpoints/cpp/chamfer_dist/chamfer_cuda.cpp:37-38)
   emd_cuda        approxmatch_forward / matchcost_*      (metrics/PyTorchEMD/cuda/emd.cpp:8-26)
   emd_assignment  forward/backward                       (metrics/emd_assignment/emd_assignment/emd.cpp:14-30)
 
@@ -44,6 +45,36 @@ def _chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1
 chamfer_3D = types.ModuleType("chamfer_3D")
 chamfer_3D.forward = _chamfer_forward
 chamfer_3D.backward = _chamfer_backward
+
+
+def _chamfer_dist_forward(xyz1, xyz2):
+    """chamfer_dist/chamfer.cu:147: the arithmetic of chamfer3D.cu with the allocation moved inside
+    -> [dist1 f32[b,n], dist2 f32[b,m], idx1 i32[b,n], idx2 i32[b,m]], fresh tensors"""
+    check(xyz1, F32, "xyz1"), check(xyz2, F32, "xyz2")
+    b, n, _ = xyz1.shape
+    m = xyz2.shape[1]
+    dev = xyz1.device
+    dist1, dist2 = torch.zeros(b, n, dtype=F32, device=dev), torch.zeros(b, m, dtype=F32, device=dev)
+    idx1, idx2 = torch.zeros(b, n, dtype=I32, device=dev), torch.zeros(b, m, dtype=I32, device=dev)
+    if not _chamfer_forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
+        raise P2PBError("chamfer.forward failed")
+    return [dist1, dist2, idx1, idx2]
+
+
+def _chamfer_dist_backward(xyz1, xyz2, idx1, idx2, grad_dist1, grad_dist2):
+    """chamfer_dist/chamfer.cu:203 -> [grad_xyz1 f32[b,n,3], grad_xyz2 f32[b,m,3]], fresh tensors"""
+    for t, n_ in ((xyz1, "xyz1"), (xyz2, "xyz2"), (grad_dist1, "grad_dist1"), (grad_dist2, "grad_dist2")):
+        check(t, F32, n_)
+    check(idx1, I32, "idx1"), check(idx2, I32, "idx2")
+    grad_xyz1, grad_xyz2 = torch.zeros_like(xyz1), torch.zeros_like(xyz2)
+    if not _chamfer_backward(xyz1, xyz2, grad_xyz1, grad_xyz2, grad_dist1, grad_dist2, idx1, idx2):
+        raise P2PBError("chamfer.backward failed")
+    return [grad_xyz1, grad_xyz2]
+
+
+chamfer = types.ModuleType("chamfer")
+chamfer.forward = _chamfer_dist_forward
+chamfer.backward = _chamfer_dist_backward
 
 
 def _approxmatch_forward(xyz1, xyz2):

@@ -8,12 +8,14 @@ argument meaning:
                                               (metrics/PyTorchEMD/emd.py:5-49, emd_nograd.py:7-45)
   emdFunction / emdModule                     (metrics/emd_assignment/emd_module.py:30-96)
   calculate_cd_cuda / calculate_emd_cuda      (metrics/metrics.py:56-108, chunked evaluation)
+  ChamferFunction / ChamferDistanceL2 / ChamferDistanceL2_split / ChamferDistanceL1
+                                              (third_party/openpoints/cpp/chamfer_dist/__init__.py:12-93)
 """
 import torch
 from torch import nn
 from torch.autograd import Function
 
-from .metric_modules import chamfer_3D, emd_assignment, emd_cuda
+from .metric_modules import chamfer, chamfer_3D, emd_assignment, emd_cuda
 
 
 class chamfer_3DFunction(Function):
@@ -63,6 +65,54 @@ class chamfer_3DDist_nograd(nn.Module):
 def chamfer_dist_nograd(x, y):
     d1, d2, _, _ = chamfer_3DDist_nograd()(x, y)
     return d1, d2
+
+
+class ChamferFunction(Function):
+    """xyz1 f32[b,n,3], xyz2 f32[b,m,3] -> (dist1 f32[b,n], dist2 f32[b,m]): squared distance to the nearest point of the other cloud"""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2):
+        dist1, dist2, idx1, idx2 = chamfer.forward(xyz1, xyz2)
+        ctx.save_for_backward(xyz1, xyz2, idx1, idx2)
+        return dist1, dist2
+
+    @staticmethod
+    def backward(ctx, grad_dist1, grad_dist2):
+        xyz1, xyz2, idx1, idx2 = ctx.saved_tensors
+        grad_xyz1, grad_xyz2 = chamfer.backward(xyz1, xyz2, idx1, idx2, grad_dist1.contiguous(), grad_dist2.contiguous())
+        return grad_xyz1, grad_xyz2
+
+
+class _ChamferDistance(nn.Module):
+    """ignore_zeros: at batch size 1, points whose coordinates sum to zero (padding) are dropped from both clouds"""
+
+    def __init__(self, ignore_zeros=False):
+        super().__init__()
+        self.ignore_zeros = ignore_zeros
+
+    def distances(self, xyz1, xyz2):
+        if xyz1.size(0) == 1 and self.ignore_zeros:
+            xyz1 = xyz1[torch.sum(xyz1, dim=2).ne(0)].unsqueeze(dim=0)
+            xyz2 = xyz2[torch.sum(xyz2, dim=2).ne(0)].unsqueeze(dim=0)
+        return ChamferFunction.apply(xyz1, xyz2)
+
+
+class ChamferDistanceL2(_ChamferDistance):
+    def forward(self, xyz1, xyz2):
+        dist1, dist2 = self.distances(xyz1, xyz2)
+        return torch.mean(dist1) + torch.mean(dist2)
+
+
+class ChamferDistanceL2_split(_ChamferDistance):
+    def forward(self, xyz1, xyz2):
+        dist1, dist2 = self.distances(xyz1, xyz2)
+        return torch.mean(dist1), torch.mean(dist2)
+
+
+class ChamferDistanceL1(_ChamferDistance):
+    def forward(self, xyz1, xyz2):
+        dist1, dist2 = self.distances(xyz1, xyz2)
+        return (torch.mean(torch.sqrt(dist1)) + torch.mean(torch.sqrt(dist2))) / 2
 
 
 class EarthMoverDistanceFunction(Function):
