@@ -30,8 +30,8 @@ extern "C" {
 
 #define P2PB_EINVAL (-22)
 
-/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (12: the eleven
- * p2pb_pointops_* operators added; 11: the five p2pb_pn2_* operators added; 10: the GroupNorm finisher is
+/* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (13: the four
+ * p2pb_imgfeat_* entry points added; 12: the eleven p2pb_pointops_* operators added; 11: the five p2pb_pn2_* operators added; 10: the GroupNorm finisher is
  * passed to p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather as fin_* arguments, the three
  * entry points that armed one for the thread's next launch removed; 9: the set metrics
  * p2pb_pairwise_chamfer / p2pb_pairwise_emd / p2pb_occupancy_* added; 8: p2pb_softmax_attention_* added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
@@ -39,7 +39,7 @@ extern "C" {
  * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
  * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
-#define P2PB_ABI_VERSION 12
+#define P2PB_ABI_VERSION 13
 
 /* library / device info --------------------------------------------------------------------- */
 int p2pb_version(void);            /* == P2PB_ABI_VERSION of the header the library was built from */
@@ -791,6 +791,47 @@ int p2pb_occupancy_grid_cells(int resolution, int clip_sphere);
 size_t p2pb_occupancy_ws_bytes(int resolution);
 int p2pb_occupancy_counts(int clouds, int npts, int resolution, int clip_sphere, const float *pts, int *counters,
                           int *bernoulli, void *ws, void *stream);
+
+/* image features onto a scan ----------------------------------------------------------------------------------
+ * Replaces the per-point stages of process_scene, data/processing/image_features.py:329-514 (the reference runs them on the
+ * host with numba, torch indexing and a KD-tree). Python side: p2p_bridge_amd/image_features.py. No float atomics anywhere:
+ * the same inputs give the same bits.
+ *
+ * p2pb_imgfeat_visibility: project_point_cloud_batch (:114-143) + filter_points_batch_with_occlusion (:146-190) for b frames.
+ *   points f64[n,3], rotation f64[b,3,3], translation f64[b,3], camera f64[b,3,3] -> valid u8[b,n] (0 / 1), xy i32[b,n,2].
+ *   Projection in fp64 in this order: cam = ((r0*x + r1*y) + r2*z) + t per row, then (k0*X + k1*Y) + k2*Z per row of the
+ *   camera matrix, then x = u / w, y = v / w (IEEE divides), depth = w.
+ *   A point is INSIDE iff -1 < x < width, -1 < y < height and min_depth < depth < max_depth, all strict and all decided in
+ *   floating point before any conversion (NaN, +-inf, w <= 0 and coordinates beyond the int range are outside); its pixel is
+ *   (trunc(x), trunc(y)), truncation toward zero, so x in (-1, 0) is column 0. valid[f,i] = INSIDE and depth strictly below
+ *   the smallest depth of the inside points j < i of the same pixel of frame f (the first point of a pixel is valid, an equal
+ *   depth is not, a later nearer point does not revoke an earlier farther one): the records of the running minimum of each
+ *   pixel in index order, the reference's fresh-per-frame depth buffer. xy[f,i] = the truncated pixel of every INSIDE point
+ *   (valid or occluded), (-1, -1) for the others.
+ *   ws: p2pb_imgfeat_visibility_ws_bytes(b, n, width, height) bytes, 8-byte aligned. b <= 65535, b*n and width*height < 2^31.
+ *   Cost note: a pixel holding L inside points costs one wave L^2/64 steps once L > 64.
+ * p2pb_imgfeat_fuse: map_image_features_to_filtered_ptc_batch_torch (:223-250) + update_features_batched_torch (:253-279),
+ *   all b frames of a batch in one launch, frame f's rows paired with frame f's points. maps f16[b,hmap,wmap,c] channel-last;
+ *   a valid point takes the row at [clamp(xy.y, 0, hmap-1), clamp(xy.x, 0, wmap-1)]. mean f16[n,c] and count i32[n] are
+ *   updated in place, per frame 0..b-1 in order: count += 1, d = f16(f32(new) - f32(mean)), q = f16(f32(d) / f32(count)),
+ *   mean = f16(f32(mean) + f32(q)). Any c >= 1 (16-byte vectors when c % 8 == 0 and maps / mean are 16-byte aligned).
+ * p2pb_imgfeat_fill_round: one round of interpolate_missing_features (:282-326) as a wavefront. missing i32[m] (the points with
+ *   count 0, ascending), nbr i32[m,k] (their k nearest points of the cloud, the point itself among them; k <= 32), feat
+ *   f16[n,c] in place, done_round i32[n] (zeros before round 1), round >= 1, remaining i32[1] (m before round 1). A missing
+ *   point i not yet done is READY iff every neighbour j < i with count 0 has 1 <= done_round[j] < round. A ready point takes
+ *   the rows of its neighbours j != i with count[j] > 0, or count[j] == 0 and j < i (filled rows), drops the all-zero ones,
+ *   and stores the per-channel median (mean of the two middle values in fp32 for an even number, one rounding to fp16; zeros
+ *   if no row is left; NaN if a value is NaN), sets done_round[i] = round and decrements remaining. The caller launches
+ *   rounds 1, 2, ... until remaining is 0; the lowest unfinished point is always ready.
+ * -> 0, P2PB_EINVAL for bad sizes or NULL operands. */
+size_t p2pb_imgfeat_visibility_ws_bytes(int b, int n, int width, int height);
+int p2pb_imgfeat_visibility(int b, int n, const double *points, const double *rotation, const double *translation,
+                            const double *camera, int width, int height, double min_depth, double max_depth,
+                            unsigned char *valid, int *xy, void *ws, void *stream);
+int p2pb_imgfeat_fuse(int b, int n, int c, int hmap, int wmap, const void *maps, const unsigned char *valid, const int *xy,
+                      void *mean, int *count, void *stream);
+int p2pb_imgfeat_fill_round(int m, int n, int c, int k, const int *missing, const int *nbr, const int *count, void *feat,
+                            int *done_round, int round, int *remaining, void *stream);
 
 #ifdef __cplusplus
 }

@@ -42,9 +42,10 @@ SYMBOLS = [
     "p2pb_pointops_grouping_backward", "p2pb_pointops_interpolation_forward", "p2pb_pointops_interpolation_backward",
     "p2pb_pointops_subtraction_forward", "p2pb_pointops_subtraction_backward", "p2pb_pointops_aggregation_forward",
     "p2pb_pointops_aggregation_backward",
+    "p2pb_imgfeat_visibility_ws_bytes", "p2pb_imgfeat_visibility", "p2pb_imgfeat_fuse", "p2pb_imgfeat_fill_round",
 ]
 
-ABI_VERSION = 12  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
+ABI_VERSION = 13  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
 
 _lib = None
 
@@ -84,6 +85,7 @@ def lib():
         _lib.p2pb_pairwise_chamfer_ws_bytes.restype = ctypes.c_size_t
         _lib.p2pb_pairwise_emd_ws_bytes.restype = ctypes.c_size_t
         _lib.p2pb_occupancy_ws_bytes.restype = ctypes.c_size_t
+        _lib.p2pb_imgfeat_visibility_ws_bytes.restype = ctypes.c_size_t
         have = _lib.p2pb_version() if hasattr(_lib, "p2pb_version") else None
         if have != ABI_VERSION:
             bad, _lib = _lib, None
