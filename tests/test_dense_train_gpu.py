@@ -221,18 +221,27 @@ def test_conv_norm_act_forward_backward(kind, b, ci, co, shape, swish):
         assert _rel(got[k], v.grad) < tol, (k, _rel(got[k], v.grad))
 
 
-@pytest.mark.parametrize("b,ci,co,r,n", [(3, 35, 32, 32, 2048), (2, 64, 64, 32, 1500), (4, 128, 64, 16, 512), (2, 24, 40, 16, 300),
-                                         (1, 8, 8, 32, 1)])
-def test_sparse_weight_gradient_of_a_first_convolution(b, ci, co, r, n):
+@pytest.mark.parametrize("b,ci,co,r,n,pattern", [
+    pytest.param(*c, None, id="-".join(map(str, c))) for c in [(3, 35, 32, 32, 2048), (2, 64, 64, 32, 1500), (4, 128, 64, 16, 512),
+                                                              (2, 24, 40, 16, 300), (1, 8, 8, 32, 1)]
+] + [pytest.param(2, 19, 40, 16, 4096, "full", id="2-19-40-16-4096-full"), pytest.param(2, 35, 32, 32, 8, "corners", id="2-35-32-32-8-corners")])
+def test_sparse_weight_gradient_of_a_first_convolution(b, ci, co, r, n, pattern):
     """round 5 (csrc/wgrad_occ.hip conv3d_k3_wgrad_occ_kernel): the weight gradient of a PVConv's first convolution over the occupied
     voxels only -- x = avg_voxelize(features) is zero elsewhere -- against torch's fp64 convolution backward and against the dense
-    kernel; grid-boundary voxels, ragged channel counts, a single point"""
+    kernel; grid-boundary voxels, ragged channel counts, a single point; pattern: the occupancy of oracle/occupancy_patterns.py,
+    every occupied voxel once (the full grid: no voxel to skip; the 8 grid corners alone)"""
     from p2p_bridge_amd import dense, layers as L
 
     torch.manual_seed(b * 1000 + ci)
     feats = torch.randn(b, ci, n, device="cuda", requires_grad=True)
-    vox = torch.randint(0, r, (b, 3, n), device="cuda", dtype=torch.int32)
-    vox[:, :, : max(1, n // 8)] = torch.randint(0, 2, (b, 3, max(1, n // 8)), device="cuda", dtype=torch.int32) * (r - 1)  # corners / faces
+    if pattern is None:
+        vox = torch.randint(0, r, (b, 3, n), device="cuda", dtype=torch.int32)
+        vox[:, :, : max(1, n // 8)] = torch.randint(0, 2, (b, 3, max(1, n // 8)), device="cuda", dtype=torch.int32) * (r - 1)  # corners / faces
+    else:
+        from oracle import occupancy_patterns
+        ids = occupancy_patterns.patterns(r)[pattern].flatten().nonzero().flatten()
+        assert len(ids) == n
+        vox = torch.stack([ids // (r * r), (ids // r) % r, ids % r]).int().expand(b, 3, n).contiguous().cuda()
     conv = torch.nn.Conv3d(ci, co, 3, padding=1).cuda()
     gy = torch.randn(b, co, r, r, r, device="cuda")
     grads = {}

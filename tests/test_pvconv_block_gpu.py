@@ -21,7 +21,8 @@ per-channel error / that channel's max|ref|:
                 r = 6: 5.3e-7 / 1.6e-6   r = 12: 1.9e-6 / 2.7e-6  r = 64: 5.1e-6 / 1.3e-5
     training    output <= 1.2e-6 / 1.7e-6; gradients (relative L2): r = 8, 16, 32: <= 6.0e-6 (bf16x6: the same), r = 12: 1.4e-5,
                 r = 64: 3.9e-5 except the second convolution's weight, 2.0e-3 (7.7e-5 of the sum of |terms|, see ABS_SUM_TOL).
-Wall time of the 55 tests on an MI355X: 11 s with torch's convolution kernels already compiled, about 30 s when the r = 64
+    "cube" clouds (CUBE_CASES: all 8 corner voxels of the grid occupied), r = 8 / 16 / 32: <= 1.4e-6 / 2.9e-6
+Wall time of the 55 tests before CUBE_CASES on an MI355X: 11 s (the 12 cube cases add 3 s) with torch's convolution kernels already compiled, about 30 s when the r = 64
 training case has to compile them first."""
 import pytest
 import torch
@@ -90,6 +91,15 @@ for _r in (16, 32):  # every value of every other axis meets r = 16 and r = 32: 
     assert any(_compact_runs(c) and c["math"] == "bf16x6" for c in _sub), _r
 
 
+# Appended: a cloud that fills the grid out to its 8 corner voxels (`_cloud` "cube": uniform in [-1, 1]^3, normalize=False, plus
+# four points at every corner). A normalised cloud lies inside the inscribed sphere, so the cases above never occupy an edge or a
+# corner voxel and their compact convolutions compute outputs of the interior and the face boundary classes only. Compact plan
+# at the case's own r for both convolutions; f16x3 with the geometry stream (pre-split operands), bf16x6 without; SE on and off.
+CUBE_CASES = [dict(r=r, math=math, se=se, cin=CHANNELS[(j + r // 8) % 4][0], cout=CHANNELS[(j + r // 8) % 4][1], cond=j % 2 == 0,
+                   sparse=True, compact=f"{r}:{r}", B=(3, 1)[j // 2 % 2], N=2048, cloud="cube", geo=math == "f16x3")
+              for r in (8, 16, 32) for j, (math, se) in enumerate((m, s) for m in ("f16x3", "bf16x6") for s in (True, False))]
+
+
 def _cid(c):
     return (f"r{c['r']}-{c['math']}-{'se' if c['se'] else 'nose'}-{c['cin']}x{c['cout']}-{'adagn' if c['cond'] else 'gn'}"
             f"-{'sparse' if c['sparse'] else 'dense'}-compact{'default' if c['compact'] is None else (c['compact'] or 'off')}"
@@ -110,6 +120,11 @@ def _cloud(kind, B, N, gen):
         return p.float(), True
     if kind == "one_voxel":
         return (0.3 + 1e-3 * torch.rand(B, 3, N, generator=gen, dtype=torch.float64)).float(), False
+    if kind == "cube":  # the whole grid, its 8 corner voxels included: 4 points at +-(1 - 1e-3) per axis each
+        p = torch.rand(B, 3, N, generator=gen, dtype=torch.float64) * 2 - 1
+        signs = torch.tensor([[1.0 if (q >> a) & 1 else -1.0 for q in range(8)] for a in range(3)], dtype=torch.float64)
+        p[:, :, :32] = (signs * (1 - 1e-3)).repeat(1, 4)
+        return p.float(), False
     p = torch.rand(B, 3, N, generator=gen, dtype=torch.float64) * 2 - 1
     p[:, 2] = 0.25
     return p.float(), True
@@ -308,7 +323,7 @@ def _geometry(coords, r, normalize):
     return Geometry({"voxel": [(0, r, normalize, 0.0)], "sa": [], "fp": []}, coords, torch.cuda.Stream())
 
 
-@pytest.mark.parametrize("c", CASES, ids=_cid)
+@pytest.mark.parametrize("c", CASES + CUBE_CASES, ids=_cid)
 def test_pvconv_block_inference(c, monkeypatch):
     """eval() + no_grad: the fused branch for r in {4, 8, 16, 32}, the dense fallback for the others -- vs float64"""
     from p2p_bridge_amd import _experiment, fused
@@ -337,6 +352,10 @@ def test_pvconv_block_inference(c, monkeypatch):
         fused.set_conv_math(prev)
     dec = _decisions(coords, c["r"], normalize)
     assert (_corner_weights(dec[0]) - dec[4].double()).abs().max().item() < 1e-6  # (the kernel's own fp32 weights)
+    if c["cloud"] == "cube":
+        r = c["r"]
+        corners = [(d * r + h) * r + w for d in (0, r - 1) for h in (0, r - 1) for w in (0, r - 1)]
+        assert (dec[2][:, corners] > 0).all(), "a corner voxel of the grid is empty"
     with torch.no_grad():
         ref = _reference(_params64(blk), feats.double(), None if cond is None else cond.double(), dec, c["r"])
     assert out.shape == ref.shape == (c["B"], c["cout"], c["N"])
