@@ -14,7 +14,8 @@
 // chip's 256 CUs -- B = 4, N = 8192 is 128 workgroups -- so the inner loop over the OTHER cloud is split over
 // blockIdx.y into `chunks` ranges: the PART forms write one partial sum per (chunk, point) and a tiny *_fin kernel adds
 // the partials in ascending chunk order (fixed order: deterministic; the sum is chunk-sequential instead of fully
-// sequential, a few ulps, far inside approxmatch's __expf tolerance). chunks == 1 keeps the single-pass kernels.
+// sequential: a few ulps per sum, but only harmless when BOTH clouds are split alike -- am_chunk_len below).
+// chunks == 1 keeps the single-pass kernels.
 
 // suml_k = 1e-9 + sum_l exp(level*d_kl) * remainR_l ; ratioL_k = remainL_k / suml_k      (:58-88)
 template <bool PART>
@@ -177,7 +178,7 @@ __global__ void am_init_kernel(int n, int m, float multiL, float multiR, float *
   if (i < m) remainR[(size_t)b * m + i] = multiR;
 }
 
-// chunks of the inner cloud per launch: enough workgroups for ~4 per CU, chunks of whole LDS tiles
+// chunks of the inner cloud per launch: enough workgroups for ~4 per CU, chunks of whole LDS tiles of the longer cloud
 static int am_chunks(int b, int n, int m) {
   static const long force = p2pb_experiment_long("am_chunks", 0);  // 1: single-pass kernels (A/B and parity experiments)
   if (force == 1) return 1;
@@ -186,6 +187,18 @@ static int am_chunks(int b, int n, int m) {
   int c = 1;
   while (base * c < 1024 && inner / (c * 2) >= EMD_TILE) c *= 2;
   return c;
+}
+
+// Length of one chunk of a cloud of `len` points: whole LDS tiles where a chunk spans at least one, else whole waves, so that the
+// SHORTER cloud is split about as often as the longer one. Both reductions must be chunked alike: a sequential fp32 sum of
+// positive terms drops the tails below half an ulp of the running sum, a chunked one keeps more of them. With the sums over
+// the targets chunked and the sums over the sources not (1024 x 4096: lc = 4, kc = 1 under whole-tile chunks), the sources
+// booked more mass as given than the targets booked as received at every level, and 1.7e-4 of the 4096 units stayed unplaced
+// on a few targets: per-target sums short by 4.7e-5 and the cost 1.3e-6 off float64, against 1.4e-6 and 1.9e-7 with kc = 4
+// (measured on an MI355X, tests/test_emd_exact_gpu.py; the 1.7e-4 from a CPU restatement of these kernels' arithmetic).
+static int am_chunk_len(int len, int chunks) {
+  const int per = cdiv(len, chunks), unit = per >= EMD_TILE ? EMD_TILE : 64;
+  return (per + unit - 1) / unit * unit;
 }
 
 extern "C" size_t p2pb_approxmatch_temp_floats(int b, int n, int m) {
@@ -221,8 +234,8 @@ static int approxmatch_impl(int b, int n, int m, const float *xyz1, const float 
   //   temp = remainL[b][n] | remainR[b][m] | ratioL[b][n] | ratioR[b][m] | partials[chunks][b][max(n,m)]
   float *remainL = temp, *remainR = remainL + (size_t)b * n, *ratioL = remainR + (size_t)b * m,
         *ratioR = ratioL + (size_t)b * n, *part = ratioR + (size_t)b * m;
-  const int lch = (cdiv(m, chunks) + EMD_TILE - 1) / EMD_TILE * EMD_TILE, kch = (cdiv(n, chunks) + EMD_TILE - 1) / EMD_TILE * EMD_TILE;
-  const int lc = cdiv(m, lch), kc = cdiv(n, kch);
+  const int lch = am_chunk_len(m, chunks), kch = am_chunk_len(n, chunks);
+  const int lc = cdiv(m, lch), kc = cdiv(n, kch);  // (both <= chunks: the partials fit)
   hipLaunchKernelGGL(am_init_kernel, dim3(cdiv(n > m ? n : m, 256), b), dim3(256), 0, s, n, m, multiL, multiR,
                      remainL, remainR);
   for (int j = 7; j >= -2; --j) {
