@@ -31,7 +31,8 @@ extern "C" {
 #define P2PB_EINVAL (-22)
 
 /* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (13: the four
- * p2pb_imgfeat_* entry points added; 12: the eleven p2pb_pointops_* operators added; 11: the five p2pb_pn2_* operators added; 10: the GroupNorm finisher is
+ * p2pb_imgfeat_* entry points added -- the nine p2pb_scan_* entry points came later WITHOUT a bump: they are pure additions, no
+ * existing entry point changed, and the loader's symbol check already refuses a library that lacks them; 12: the eleven p2pb_pointops_* operators added; 11: the five p2pb_pn2_* operators added; 10: the GroupNorm finisher is
  * passed to p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather as fin_* arguments, the three
  * entry points that armed one for the thread's next launch removed; 9: the set metrics
  * p2pb_pairwise_chamfer / p2pb_pairwise_emd / p2pb_occupancy_* added; 8: p2pb_softmax_attention_* added; 7: p2pb_norm_act_backward_ex, p2pb_affine_act_train; 6, since 1: p2pb_debug_gn_finisher removed, flag bit 5 of
@@ -832,6 +833,55 @@ int p2pb_imgfeat_fuse(int b, int n, int c, int hmap, int wmap, const void *maps,
                       void *mean, int *count, void *stream);
 int p2pb_imgfeat_fill_round(int m, int n, int c, int k, const int *missing, const int *nbr, const int *count, void *feat,
                             int *done_round, int round, int *remaining, void *stream);
+
+/* scan fusion ---------------------------------------------------------------------------------------------------
+ * Depth frames -> one cleaned room cloud: the GPU stages of data/scannetpp/iphone/process_dataset.py:102-283 and arkit_pcl.py
+ * (the reference runs them through Open3D's CUDA tensor geometry and cuML). Python side: p2p_bridge_amd/scan_fusion.py, which
+ * sorts keys, takes prefix sums and compacts with torch. No float atomics anywhere: the same inputs give the same bits.
+ * Squared distances are fma(dz,dz, fma(dy,dy, dx*dx)), d = point - query, as everywhere in this header.
+ *
+ * p2pb_scan_depth_valid: valid u8[npix] = 1 iff min_depth <= depth <= max_depth (fp32 compares; NaN and +-inf are 0).
+ * p2pb_scan_backproject: pix i64[n] (row-major pixel indices y*width + x, any subset), image u8[height,width,3], depth
+ *   f32[height,width]; kinv f64[9] (the inverse intrinsic, row-major) and camera_to_world f64[>= 12] (row-major, the top three
+ *   rows are read) are HOST pointers, copied before the call returns. fp64: cam = ((k0*x + k1*y) + k2) * z per row of kinv,
+ *   world = ((c0*X + c1*Y) + c2*Z) + c3 per row, one rounding -> xyz f32[n,3]; rgb f32[n,3] = the bytes as floats.
+ * p2pb_scan_cell_keys: keys i64[n] = (kx + 2^20) << 42 | (ky + 2^20) << 21 | (kz + 2^20), k = floor(p / cell) with an IEEE fp32
+ *   divide (no origin shift; -0.001 lies in cell -1). *bad (i32, zeroed by the caller) is set to 1 when a k falls outside
+ *   [-2^20, 2^20) or a coordinate is NaN; such a row's key is meaningless.
+ * p2pb_scan_segment_mean: rows perm[starts[v] .. starts[v+1]) of src f32[*,c] form segment v of m (perm: the stable argsort
+ *   of the keys, so each segment is in ascending row order). out f32[m,c] = (float)(fp64 sum in that order / count) for the
+ *   segments of at most `small` rows, one thread per (segment, channel); longer ones are NOT written.
+ * p2pb_scan_segment_mean_big: the longer ones. big i64[nbig] = their segment numbers; segment big[b] is cut into the chunks
+ *   chunk_begin[b] .. chunk_begin[b+1] (chunk_begin i64[nbig+1]) of at most p2pb_scan_big_chunk_rows() rows; chunk q covers the
+ *   sorted rows chunk_row0[q] .. + chunk_rows[q]. One workgroup per chunk adds it in fp64 in a fixed order into partial
+ *   f64[nchunks,c]; a second kernel adds a segment's chunks in chunk order, divides and rounds once.
+ * The grid of the neighbour search is the reference points sorted by p2pb_scan_cell_keys: sorted_points f32[n,3] and
+ *   sorted_keys i64[n] in the same order. Cells (x, y, z0..z1) have consecutive keys: one column of cells is one run.
+ * p2pb_scan_radius_count: counts[q] = min(limit, #{ j : sqdist <= r2 }), one thread per query. reach >= the largest
+ *   |p - q| per axis that can pass the fp32 test (the caller adds the roundings to the radius); the cells between those of
+ *   q - reach and q + reach are visited, the 27 around the query's cell when cell is the radius. Exact.
+ * p2pb_scan_knn_grid: one wave per query qidx[w] (i32[nq]; NULL: query w), rings 1..max_ring (<= 16) of cells around the
+ *   query's cell; a ring is final when the k-th smallest squared distance so far is no larger than the squared distance to
+ *   the nearest cell not yet visited (roundings of the cell index allowed for). Then out[q] = sqrtf(k-th smallest squared
+ *   distance) and unresolved[q] = 0; otherwise unresolved[q] = 1 and out[q] is not written. 1 <= k <= 64.
+ * p2pb_scan_knn_brute: the same result from a walk over all n points (any order), one wave per query; k <= n.
+ * -> 0, P2PB_EINVAL for bad sizes or NULL operands. */
+int p2pb_scan_depth_valid(int npix, const float *depth, float min_depth, float max_depth, unsigned char *valid, void *stream);
+int p2pb_scan_backproject(int n, int width, int height, const long long *pix, const unsigned char *image, const float *depth,
+                          const double *kinv, const double *camera_to_world, float *xyz, float *rgb, void *stream);
+int p2pb_scan_cell_keys(int n, const float *xyz, float cell, long long *keys, int *bad, void *stream);
+int p2pb_scan_segment_mean(long long m, int c, int small, const float *src, const long long *perm, const long long *starts,
+                           float *out, void *stream);
+int p2pb_scan_big_chunk_rows(void);
+int p2pb_scan_segment_mean_big(int nbig, int nchunks, int c, const float *src, const long long *perm, const long long *starts,
+                               const long long *big, const long long *chunk_begin, const long long *chunk_row0,
+                               const long long *chunk_rows, double *partial, float *out, void *stream);
+int p2pb_scan_radius_count(int nq, int n, const float *query, const float *sorted_points, const long long *sorted_keys,
+                           float cell, float r2, float reach, int limit, int *counts, void *stream);
+int p2pb_scan_knn_grid(int nq, int n, int k, int max_ring, const int *qidx, const float *query, const float *sorted_points,
+                       const long long *sorted_keys, float cell, float *out, unsigned char *unresolved, void *stream);
+int p2pb_scan_knn_brute(int nq, int n, int k, const int *qidx, const float *query, const float *points, float *out,
+                        void *stream);
 
 #ifdef __cplusplus
 }
