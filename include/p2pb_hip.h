@@ -31,7 +31,7 @@ extern "C" {
 #define P2PB_EINVAL (-22)
 
 /* ABI version of THIS header: bumped whenever an entry point is added, removed or changes meaning (13: the four
- * p2pb_imgfeat_* entry points added -- the nine p2pb_scan_* entry points came later WITHOUT a bump: they are pure additions, no
+ * p2pb_imgfeat_* entry points added -- the nine p2pb_scan_* and the five p2pb_pairs_* entry points came later WITHOUT a bump: they are pure additions, no
  * existing entry point changed, and the loader's symbol check already refuses a library that lacks them; 12: the eleven p2pb_pointops_* operators added; 11: the five p2pb_pn2_* operators added; 10: the GroupNorm finisher is
  * passed to p2pb_pointwise_conv_forward / _conv_pool_forward / _conv_pool_gather as fin_* arguments, the three
  * entry points that armed one for the thread's next launch removed; 9: the set metrics
@@ -882,6 +882,48 @@ int p2pb_scan_knn_grid(int nq, int n, int k, int max_ring, const int *qidx, cons
                        const long long *sorted_keys, float cell, float *out, unsigned char *unresolved, void *stream);
 int p2pb_scan_knn_brute(int nq, int n, int k, const int *qidx, const float *query, const float *points, float *out,
                         void *stream);
+
+/* room training pairs ---------------------------------------------------------------------------------------------
+ * (noisy patch, aligned clean patch) pairs of a room: the device stages of data/preprocess_batches.py and
+ * data/processing/utils.py:create_spherical_batches (the reference runs them through Open3D, cuML and a Python double loop).
+ * Python side: p2p_bridge_amd/room_pairs.py. No float atomics: the same inputs give the same bits. Clean patches are RAGGED:
+ * ref f32[total,3] holds them one after another, patch p is rows ref_off[p] .. ref_off[p+1] (ref_off i64[P+1], DEVICE memory).
+ * The entry points that take ref_off copy it to the host and wait for the stream (they are not for stream capture): offsets
+ * that are negative, decreasing or beyond `total` are P2PB_EINVAL before any kernel runs.
+ *
+ * p2pb_pairs_tri_areas: area f64[F] = |cross(b - a, c - a)| / 2 in fp64 of faces i32[F,3] over verts f32[V,3]; a face with a
+ *   vertex index outside [0, V) has area 0 and sets *bad (i32, zeroed by the caller) to 1.
+ * p2pb_pairs_sample_mesh: cdf f64[F] = the inclusive prefix sum of the areas, u f64[n,3] in [0,1). face[i] = the first f with
+ *   cdf[f] > u0 * cdf[F-1] (numpy's searchsorted(cdf, u0 * total, side="right"), at most F-1: a zero-area triangle is never
+ *   drawn); s = sqrt(u1), w = (1 - s, s * (1 - u2), s * u2); xyz[i] = (float)((w0*a + w1*b) + w2*c) per axis in fp64, one
+ *   rounding; rgb[i] the same over vcol f32[V,3] (vcol and rgb NULL: no colours).
+ * p2pb_pairs_knn: query f32[P,s,3] -> idx i32[P,s,K] (the index INSIDE the patch) and dist2 f32[P,s,K] (may be NULL): the K
+ *   smallest fma(dz,dz, fma(dy,dy, dx*dx)), d = point - query, ascending, ties by ascending index -- the contract and the bits
+ *   of p2pb_knn_points. 1 <= K <= 128; a patch of fewer than K points is P2PB_EINVAL. One launch, one wave per query, no
+ *   scratch: the clean patch streams through LDS.
+ * p2pb_pairs_unique_assign: nn i32[P,s,K] (indices inside the patch). assign[p,i], i ascending = the first entry of nn[p,i,:]
+ *   that no point j < i of the patch has taken; all K taken: nn[p,i,0], and the point takes nothing. Computed in parallel
+ *   (deferred acceptance on integer atomicMin, one workgroup per patch), bit-equal to that sequential rule. unique[p] = the
+ *   number of points that took an entry = the number of distinct values in assign[p] (a fall-back value nn[p,i,0] is one that
+ *   an earlier point took). owner i32[total] is scratch (no need to initialise it). Entries of nn outside
+ *   [0, ref_off[p+1] - ref_off[p]) count as taken; a fall-back to such an entry puts a value into assign[p] that nobody took,
+ *   and unique[p] does NOT count it. 1 <= K <= 128.
+ * p2pb_pairs_finish: center[p] = (float)(fp64 sum of noisy[p,:,a] in index order / s); d = noisy - center in fp32; scale[p] =
+ *   max_i (float)sqrt(dx*dx + dy*dy + dz*dz in fp64); noisy_out[p,i] = (d / scale, noisy_rgb[p,i]); clean_out[p,i] =
+ *   ((ref[j] - center) / scale, ref_rgb[j]), j = ref_off[p] + assign[p,i] (fp32 subtract and IEEE divide; an assign outside
+ *   the patch gives a row of NaN). noisy f32[P,s,3], noisy_rgb f32[P,s,3], ref_rgb f32[total,3], outputs f32[P,s,6],
+ *   center f32[P,3], scale f32[P].
+ * -> 0, P2PB_EINVAL for bad sizes, offsets or NULL operands. */
+int p2pb_pairs_tri_areas(int nverts, int nfaces, const float *verts, const int *faces, double *area, int *bad, void *stream);
+int p2pb_pairs_sample_mesh(int nverts, int nfaces, int n, const float *verts, const float *vcol, const int *faces,
+                           const double *cdf, const double *u, int *face, float *xyz, float *rgb, void *stream);
+int p2pb_pairs_knn(int npatch, int s, int k, int total, const float *query, const float *ref, const long long *ref_off,
+                   int *idx, float *dist2, void *stream);
+int p2pb_pairs_unique_assign(int npatch, int s, int k, int total, const int *nn, const long long *ref_off, int *owner,
+                             int *assign, int *unique, void *stream);
+int p2pb_pairs_finish(int npatch, int s, int total, const float *noisy, const float *noisy_rgb, const float *ref,
+                      const float *ref_rgb, const long long *ref_off, const int *assign, float *clean_out, float *noisy_out,
+                      float *center, float *scale, void *stream);
 
 #ifdef __cplusplus
 }

@@ -29,13 +29,16 @@ import torch
 from . import metrics as M
 
 MULTIPLIER = 10 ** 3
+_PLY_RGB = ("red", "green", "blue")
 COLUMNS = ["model_config", "point_dist", "face_dist", "cd_pred_gt", "cd_gt_pred"]
 _PLY_TYPES = {"char": "b", "int8": "b", "uchar": "B", "uint8": "B", "short": "h", "int16": "h", "ushort": "H", "uint16": "H",
               "int": "i", "int32": "i", "uint": "I", "uint32": "I", "float": "f", "float32": "f", "double": "d", "float64": "d"}
 
 
-def read_ply(path: str) -> Dict[str, Optional[np.ndarray]]:
-    """-> {"points": f64[N,3], "faces": i64[F,3] | None}; ascii, binary_little_endian and binary_big_endian"""
+def read_ply(path: str, colors: bool = False) -> Dict[str, Optional[np.ndarray]]:
+    """-> {"points": f64[N,3], "faces": i64[F,3] | None}; ascii, binary_little_endian and binary_big_endian.
+    colors=True adds "colors": f64[N,3] | None, the vertex properties red green blue as Open3D hands them out (integer
+    properties divided by 255, floating-point ones as stored)."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -56,6 +59,8 @@ def read_ply(path: str) -> Dict[str, Optional[np.ndarray]]:
             elif tok[0] == "end_header":
                 break
         out = {"points": None, "faces": None}
+        if colors:
+            out["colors"] = None
         if fmt == "ascii":
             words = f.read().split()
             pos = 0
@@ -72,7 +77,7 @@ def read_ply(path: str) -> Dict[str, Optional[np.ndarray]]:
                             row.append([int(w) for w in words[pos + 1:pos + 1 + k]])
                             pos += 1 + k
                     rows.append(row)
-                _collect(out, name, props, rows)
+                _collect(out, name, props, rows, colors)
             return out
         end = "<" if fmt == "binary_little_endian" else ">"
         for name, count, props in elements:
@@ -81,6 +86,8 @@ def read_ply(path: str) -> Dict[str, Optional[np.ndarray]]:
                 rec = np.frombuffer(f.read(dt.itemsize * count), dtype=dt, count=count)
                 if name == "vertex":
                     out["points"] = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float64)
+                    if colors and all(c in rec.dtype.names for c in _PLY_RGB):
+                        out["colors"] = np.stack([rec[c] for c in _PLY_RGB], 1).astype(np.float64) / _rgb_unit(props)
                 continue
             rows = []
             for _ in range(count):
@@ -94,15 +101,24 @@ def read_ply(path: str) -> Dict[str, Optional[np.ndarray]]:
                         k = struct.unpack(end + ck, f.read(struct.calcsize(ck)))[0]
                         row.append(list(struct.unpack(end + ci * k, f.read(struct.calcsize(ci) * k))))
                 rows.append(row)
-            _collect(out, name, props, rows)
+            _collect(out, name, props, rows, colors)
         return out
 
 
-def _collect(out, name, props, rows):
+def _rgb_unit(props):
+    """255 when the vertex colours are stored as integers, 1 when as floats"""
+    kinds = {p[2]: p[1] for p in props if p[0] == "scalar"}
+    return 1.0 if _PLY_TYPES[kinds["red"]] in "fd" else 255.0
+
+
+def _collect(out, name, props, rows, colors=False):
     names = [p[-1] for p in props]
     if name == "vertex":
         ix = [names.index(a) for a in "xyz"]
         out["points"] = np.asarray([[r[i] for i in ix] for r in rows], dtype=np.float64).reshape(-1, 3)
+        if colors and all(c in names for c in _PLY_RGB):
+            ix = [names.index(c) for c in _PLY_RGB]
+            out["colors"] = np.asarray([[r[i] for i in ix] for r in rows], dtype=np.float64).reshape(-1, 3) / _rgb_unit(props)
     elif name == "face":
         li = next(i for i, p in enumerate(props) if p[0] == "list")
         tris = [(r[li][0], r[li][j], r[li][j + 1]) for r in rows for j in range(1, len(r[li]) - 1)]
