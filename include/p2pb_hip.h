@@ -925,6 +925,51 @@ int p2pb_pairs_finish(int npatch, int s, int total, const float *noisy, const fl
                       const float *ref_rgb, const long long *ref_off, const int *assign, float *clean_out, float *noisy_out,
                       float *center, float *scale, void *stream);
 
+/* point-to-mesh grid ----------------------------------------------------------------------------------------------
+ * The (dist, idx) of p2pb_point_face_dist / p2pb_face_point_dist, bit for bit and ties included, from an exact search over a
+ * uniform grid (csrc/p2m_grid.hip; Python side: metrics.TriangleGrid; argument for the bounds: DESIGN.md, "Point-to-mesh
+ * grid"). Pure additions like the p2pb_scan_* and p2pb_pairs_* entry points: P2PB_ABI_VERSION stays 13. Cells and keys are
+ * those of p2pb_scan_cell_keys. tris f32[nt,3,3], points f32[np,3]; `mag` > 0 bounds every coordinate the bounds were
+ * proven for, pad = mag * 2^-19 is the absolute rounding allowance.
+ *
+ * p2pb_p2m_grid_classify: per triangle cls u8[nt] (0: prunable, box f32[nt,6] = lo xyz, hi xyz holds every point of the
+ *   region in which point_triangle_d2 can fall below the squared distance to that box times shrink[t]^2; 1: no such finite
+ *   box -- a vertex that is not finite or beyond mag, an ill-conditioned or tiny triangle with the inside test enabled, an
+ *   enlargement above 1e6 -- test it against everything) and shrink f32[nt] in (0, 1].
+ * p2pb_p2m_grid_count: counts i32[nt] = the number of cells a prunable box overlaps if that is at most `cap`, else 0;
+ *   wide u8[nt] = 1 for every triangle that gets no incidences (cls 1, over the cap, outside the key range).
+ * p2pb_p2m_grid_fill: offsets i64[nt] = the exclusive prefix sum of counts; writes keys i64[total] and ids i32[total], the
+ *   (cell key, triangle) incidences of triangle t at offsets[t] .. offsets[t] + counts[t].
+ * p2pb_p2m_grid_point_face: keys ascending with ids permuted alike (ninc >= 0 of them), wide_ids i32[nwide] the wide
+ *   triangles. One thread per point: the wide triangles, then rings 1..max_ring (<= 8) of cells around the point's cell. A
+ *   ring is final when best < (shrink * (rho cells less rounding less pad))^2 less a margin; then dist / idx are written and
+ *   unresolved[i] = 0. Otherwise (ring limit, a point that is not finite or beyond mag) unresolved[i] = 1 and dist / idx are
+ *   left alone.
+ * p2pb_p2m_grid_face_point: sorted_points f32[ns,3] ascending by sorted_keys, order i32[ns] their indices in the caller's
+ *   cloud, extra f32[nextra,3] / extra_idx i32[nextra] the points that are not in the grid (tested by every triangle). One
+ *   thread per triangle: rings 1..max_ring around the cells of its box while the ring has at most max_cols columns;
+ *   unresolved[t] as above (cls 1 included). ns may be 0 (sorted_* then unused).
+ * p2pb_p2m_point_face_subset / p2pb_p2m_face_point_subset: the brute-force result for the listed queries qidx i32[nq] only
+ *   (one wave each, over ALL triangles / points), written to dist[q], idx[q].
+ * -> 0, P2PB_EINVAL for bad sizes or NULL operands. */
+int p2pb_p2m_grid_classify(int nt, const float *tris, float min_triangle_area, float mag, float *box, float *shrink,
+                           unsigned char *cls, void *stream);
+int p2pb_p2m_grid_count(int nt, const unsigned char *cls, const float *box, float cell, int cap, int *counts,
+                        unsigned char *wide, void *stream);
+int p2pb_p2m_grid_fill(int nt, const int *counts, const long long *offsets, const float *box, float cell, long long total,
+                       long long *keys, int *ids, void *stream);
+int p2pb_p2m_grid_point_face(int np, int nt, int ninc, int nwide, int max_ring, const float *points, const float *tris,
+                             float min_triangle_area, const long long *keys, const int *ids, const int *wide_ids, float cell,
+                             float mag, float shrink, float *dist, int *idx, unsigned char *unresolved, void *stream);
+int p2pb_p2m_grid_face_point(int ns, int nt, int nextra, int max_ring, int max_cols, const float *sorted_points,
+                             const int *order, const long long *sorted_keys, const float *extra, const int *extra_idx,
+                             const float *tris, float min_triangle_area, const unsigned char *cls, const float *box, float cell,
+                             float mag, float shrink, float *dist, int *idx, unsigned char *unresolved, void *stream);
+int p2pb_p2m_point_face_subset(int nq, const int *qidx, int np, int nt, const float *points, const float *tris,
+                               float min_triangle_area, float *dist, int *idx, void *stream);
+int p2pb_p2m_face_point_subset(int nq, const int *qidx, int np, int nt, const float *points, const float *tris,
+                               float min_triangle_area, float *dist, int *idx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,9 @@ SYMBOLS = [
     "p2pb_scan_depth_valid", "p2pb_scan_backproject", "p2pb_scan_cell_keys", "p2pb_scan_segment_mean", "p2pb_scan_big_chunk_rows",
     "p2pb_scan_segment_mean_big", "p2pb_scan_radius_count", "p2pb_scan_knn_grid", "p2pb_scan_knn_brute",
     "p2pb_pairs_tri_areas", "p2pb_pairs_sample_mesh", "p2pb_pairs_knn", "p2pb_pairs_unique_assign", "p2pb_pairs_finish",
+    # point-to-mesh grid
+    "p2pb_p2m_grid_classify", "p2pb_p2m_grid_count", "p2pb_p2m_grid_fill", "p2pb_p2m_grid_point_face",
+    "p2pb_p2m_grid_face_point", "p2pb_p2m_point_face_subset", "p2pb_p2m_face_point_subset",
 ]
 
 ABI_VERSION = 13  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)

@@ -2,7 +2,8 @@
 `<root>/<scene>/{scans/, predictions<suffix>/<model>/*.{ply,xyz}}` the two one-sided Chamfer distances of each predicted
 cloud against the Faro scan and, for ScanNet++ (which ships a mesh), the point-to-face / face-to-point distances, all
 x 1000, appended to `<scene>/metrics/<model>/metrics<suffix>.csv` (already scored configurations are skipped).
-On this package's HIP metrics (`metrics.cd_unit_sphere`, `metrics.point_face_dist`: csrc/chamfer.hip, p2m.hip).
+On this package's HIP metrics (`metrics.cd_unit_sphere`, `metrics.point_face_dist`: csrc/chamfer.hip, p2m.hip and, for
+`--p2m_method grid`, the exact grid search of p2m_grid.hip with one mesh index per scene).
 
   get_mectrics (sic)        evaluate_rooms.py:21-66      (the reference's spelling is kept; `get_metrics` is an alias)
   calculate_model_metrics   :69-98
@@ -29,6 +30,7 @@ import torch
 from . import metrics as M
 
 MULTIPLIER = 10 ** 3
+P2M_METHOD_DEFAULT = "grid"  # --p2m_method when absent (same numbers either way; timing: profiles/p2m_grid_room_timing.txt)
 _PLY_RGB = ("red", "green", "blue")
 COLUMNS = ["model_config", "point_dist", "face_dist", "cd_pred_gt", "cd_gt_pred"]
 _PLY_TYPES = {"char": "b", "int8": "b", "uchar": "B", "uint8": "B", "short": "h", "int16": "h", "ushort": "H", "uint16": "H",
@@ -136,9 +138,24 @@ def _ns(args, key, default=None):
     return args.get(key, default) if isinstance(args, dict) else getattr(args, key, default)
 
 
+def _p2m_method(args):
+    return _ns(args, "p2m_method") or P2M_METHOD_DEFAULT
+
+
+def build_mesh_index(args, gt_mesh):
+    """the point-to-mesh grid of a scene's mesh (None: brute force, or no mesh): built once, handed to every get_mectrics call
+    of that scene as `mesh_index`"""
+    if gt_mesh is None or _ns(args, "dataset") != "snpp" or _p2m_method(args) != "grid":
+        return None
+    return M.mesh_triangle_grid(torch.as_tensor(gt_mesh["points"]).float().cuda(),
+                                torch.as_tensor(gt_mesh["faces"]).long().cuda(), normalize=bool(_ns(args, "normalize")))
+
+
 @torch.no_grad()
-def get_mectrics(args, gt, pred, gt_mesh=None) -> dict:
-    """args.dataset in {snpp, arkit}, args.normalize; gt / pred: clouds [N,3]; gt_mesh: {"points", "faces"} (snpp)"""
+def get_mectrics(args, gt, pred, gt_mesh=None, mesh_index=None) -> dict:
+    """args.dataset in {snpp, arkit}, args.normalize, args.p2m_method in {grid, brute} (absent: P2M_METHOD_DEFAULT); gt /
+    pred: clouds [N,3]; gt_mesh: {"points", "faces"} (snpp); mesh_index: build_mesh_index(args, gt_mesh), built here if
+    absent. Both methods return the same floats."""
     dev = "cuda"
     gt = torch.as_tensor(np.asarray(gt)).float().to(dev)
     pred = torch.as_tensor(np.asarray(pred)).float().to(dev)
@@ -147,7 +164,11 @@ def get_mectrics(args, gt, pred, gt_mesh=None) -> dict:
         assert gt_mesh is not None, "Ground truth mesh is required for SNPP dataset"
         verts = torch.as_tensor(gt_mesh["points"]).float().to(dev)
         faces = torch.as_tensor(gt_mesh["faces"]).long().to(dev)
-        pd, fd = M.point_face_dist(pred, verts, faces, normalize=bool(_ns(args, "normalize")))
+        method = _p2m_method(args)
+        if method == "grid" and mesh_index is None:
+            mesh_index = build_mesh_index(args, gt_mesh)
+        pd, fd = M.point_face_dist(pred, verts, faces, normalize=bool(_ns(args, "normalize")), method=method,
+                                   grid=mesh_index if method == "grid" else None)
         data["point_dist"], data["face_dist"] = pd * MULTIPLIER, fd * MULTIPLIER
     if pred.ndim == 2:
         pred, gt = pred.unsqueeze(0), gt.unsqueeze(0)
@@ -160,7 +181,11 @@ get_metrics = get_mectrics
 
 
 def calculate_model_metrics(data: Dict, model_name: str, args) -> Dict:
-    return {cfg: get_mectrics(args, data["faro"], pred, gt_mesh=data["faro_mesh"]) for cfg, pred in data["models"][model_name].items()}
+    preds = data["models"][model_name]
+    if preds and "mesh_index" not in data:  # once per scene, for every model and prediction of it
+        data["mesh_index"] = build_mesh_index(args, data["faro_mesh"])
+    return {cfg: get_mectrics(args, data["faro"], pred, gt_mesh=data["faro_mesh"], mesh_index=data.get("mesh_index"))
+            for cfg, pred in preds.items()}
 
 
 def _scored(model_dir, args):
@@ -243,6 +268,8 @@ def main(argv=None):
     ap.add_argument("--single_dir", action="store_true")
     ap.add_argument("--normalize", action="store_true")
     ap.add_argument("--suffix", default="")
+    ap.add_argument("--p2m_method", choices=["grid", "brute"], default=P2M_METHOD_DEFAULT,
+                    help="point-to-mesh search: exact grid (csrc/p2m_grid.hip) or every pair (csrc/p2m.hip); same numbers")
     args = ap.parse_args(argv)
     for f in os.listdir(args.data_root):
         handle_scene(os.path.join(args.data_root, f), args)

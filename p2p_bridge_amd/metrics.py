@@ -274,43 +274,99 @@ def _p2m(fn, points, tris, n_out, min_triangle_area):
     return d, idx.long()
 
 
-def point_face_distance(points, tris, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA):
-    """points f32[P,3], tris f32[T,3,3] -> (squared distance of every point to its closest triangle [P], its index)"""
+_P2M_METHODS = ("brute", "grid")
+
+
+def _p2m_grid(grid, tris, min_triangle_area, method):
+    """the mesh index of a method="grid" call: the caller's (checked against tris) or one built for this call"""
+    from .p2m_grid import TriangleGrid
+
+    if method not in _P2M_METHODS:
+        raise ValueError(f"method must be one of {_P2M_METHODS}, got {method!r}")
+    if method == "brute":
+        if grid is not None:
+            raise ValueError("a TriangleGrid goes with method='grid'")
+        return None
+    if grid is None:
+        return TriangleGrid(tris, min_triangle_area)
+    if grid.min_triangle_area != float(min_triangle_area) or grid.tris.shape != tris.shape or not torch.equal(grid.tris, tris):
+        raise ValueError("the TriangleGrid was built for another mesh or min_triangle_area")
+    return grid
+
+
+def point_face_distance(points, tris, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA, method="brute", grid=None,
+                        return_stats=False):
+    """points f32[P,3], tris f32[T,3,3] -> (squared distance of every point to its closest triangle [P], its index).
+    method="grid": the same two tensors, bit for bit, from the exact grid search of csrc/p2m_grid.hip (grid: a TriangleGrid
+    of tris built earlier; return_stats=True appends its stats dict)."""
+    g = _p2m_grid(grid, tris.contiguous(), min_triangle_area, method)
+    if g is not None:
+        return g.point_face(points, return_stats=return_stats)
+    if return_stats:
+        raise ValueError("return_stats goes with method='grid'")
     return _p2m("p2pb_point_face_dist", points.contiguous(), tris.contiguous(), points.shape[0], min_triangle_area)
 
 
-def face_point_distance(points, tris, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA):
-    """-> (squared distance of every triangle to its closest point [T], its index)"""
+def face_point_distance(points, tris, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA, method="brute", grid=None,
+                        return_stats=False):
+    """-> (squared distance of every triangle to its closest point [T], its index); method, grid, return_stats as above"""
+    g = _p2m_grid(grid, tris.contiguous(), min_triangle_area, method)
+    if g is not None:
+        return g.face_point(points, return_stats=return_stats)
+    if return_stats:
+        raise ValueError("return_stats goes with method='grid'")
     return _p2m("p2pb_face_point_dist", points.contiguous(), tris.contiguous(), tris.shape[0], min_triangle_area)
 
 
 @torch.no_grad()
-def point_mesh_face_distance(pcl, verts, faces, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA):
+def point_mesh_face_distance(pcl, verts, faces, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA, method="brute", grid=None):
     """(point_dist, face_dist) of metrics/p2m.py:307-375 for one (mesh, cloud) pair: mean squared distance of the
-    points to the mesh and of the faces to the cloud"""
+    points to the mesh and of the faces to the cloud. method="grid" builds ONE mesh index for both directions (or takes
+    the caller's `grid`)."""
     tris = verts[faces.long()].contiguous()
-    return (point_face_distance(pcl, tris, min_triangle_area)[0].mean(),
-            face_point_distance(pcl, tris, min_triangle_area)[0].mean())
+    grid = _p2m_grid(grid, tris, min_triangle_area, method)
+    return (point_face_distance(pcl, tris, min_triangle_area, method, grid)[0].mean(),
+            face_point_distance(pcl, tris, min_triangle_area, method, grid)[0].mean())
 
 
 @torch.no_grad()
-def point_face_dist(pcl, verts, faces, normalize=True):
+def mesh_triangle_grid(verts, faces, normalize=True, min_triangle_area=_DEFAULT_MIN_TRIANGLE_AREA):
+    """the TriangleGrid that point_face_dist(..., verts, faces, normalize, method="grid", grid=...) accepts: built once per
+    mesh, reused for every cloud scored against it"""
+    from .p2m_grid import TriangleGrid
+
+    verts = verts.cuda()
+    if normalize:
+        verts = normalize_sphere(verts.unsqueeze(0))[0][0]
+    return TriangleGrid(verts[faces.cuda().long()].contiguous(), min_triangle_area)
+
+
+@torch.no_grad()
+def point_face_dist(pcl, verts, faces, normalize=True, method="brute", grid=None):
     """metrics/metrics.py:198-226 -> (point_dist, face_dist) floats; pcl [N,3], verts [M,3], faces i64[T,3]"""
     assert pcl.dim() == 2 and verts.dim() == 2 and faces.dim() == 2, "Batch is not supported."
     if normalize:
         verts, center, scale = normalize_sphere(verts.unsqueeze(0))
         verts = verts[0]
         pcl = normalize_pcl(pcl.unsqueeze(0), center=center, scale=scale)[0]
-    pd, fd = point_mesh_face_distance(pcl.cuda(), verts.cuda(), faces.cuda())
+    pd, fd = point_mesh_face_distance(pcl.cuda(), verts.cuda(), faces.cuda(), method=method, grid=grid)
     return pd.item(), fd.item()
 
 
 @torch.no_grad()
-def point_mesh_bidir_distance_single_unit_sphere(pcl, verts, faces):
+def point_mesh_bidir_distance_single_unit_sphere(pcl, verts, faces, method="brute"):
     """models/evaluation.py:329-353: pytorch3d.loss.point_mesh_face_distance(min_triangle_area=0.0) on the mesh's
     unit sphere = point_dist + face_dist"""
     assert pcl.dim() == 2 and verts.dim() == 2 and faces.dim() == 2, "Batch is not supported."
     verts, center, scale = normalize_sphere(verts.unsqueeze(0))
     pcl = normalize_pcl(pcl.unsqueeze(0), center=center, scale=scale)[0]
-    pd, fd = point_mesh_face_distance(pcl, verts[0], faces, min_triangle_area=0.0)
+    pd, fd = point_mesh_face_distance(pcl, verts[0], faces, min_triangle_area=0.0, method=method)
     return pd + fd
+
+
+def __getattr__(name):  # metrics.TriangleGrid / metrics.plan_triangle_grid without importing the grid module up front
+    if name in ("TriangleGrid", "plan_triangle_grid"):
+        from . import p2m_grid
+
+        return getattr(p2m_grid, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
