@@ -9,8 +9,12 @@ existing Python wrapper while the wrapper's torch.empty / torch.zeros / ... are 
      next to each family (nothing here widens one) -- NaN propagates, so this is what turns an over-read into a failure.
 `test_planted_overrun_is_caught` proves the net is live on the device. Workspaces are exempt from 2, not from 1; so are the two
 results that the ABI header documents as written in part (`listed_only`, `active_only`: the cases cite the header).
-Wrappers of fused.py that no case calls, and so are NOT held here: interp_add, pw_conv_pool_gather, voxel_sort /
-voxelize_cl_gather, conv3d_presplit, conv3d_far_field_gn, pvconv_tail, minmax_act_pool_gn, affine_act.
+Wrappers of fused.py that no case calls here are held in tests/test_fused_discipline_gpu.py, same arena, same four checks, host
+references only: interp_add, pw_conv_pool_gather, voxel_sort / voxelize_cl_gather, conv3d_presplit and the `pre=True`
+convolutions, conv3d_far_field_gn, pvconv_tail, minmax_act_pool_gn, affine_act, and the arms this file passes by (pw_conv's
+point_major / ci_lo, ci_hi / fin= / wide-layer pre-pass, devoxelize_affine's add=, minmax_act and affine_act_max on host-built
+inputs). Still NOT held of fused.py: no wrapper that launches a kernel; operand_audit is a diagnostic around the wrappers
+above whose own arithmetic is torch's.
 
 Run time on an MI355X: 111 cases in 9.3 s on their own; the whole `-m gpu` suite took 293.9 s with this file in it (710 tests),
 so about 285 s without it (the parent commit's 599 tests, same box, same run).
