@@ -2,14 +2,13 @@
 // (xyz f32[B,N,3]; PN2 = third_party/openpoints/cpp/pointnet2_batch/src):
 //   p2pb_pn2_ball_query              (PN2/ball_query_gpu.cu:15)
 //   p2pb_pn2_three_nn                (PN2/interpolate_gpu.cu:16)
-//   p2pb_pn2_fps                     (PN2/sampling_gpu.cu:101)
 //   p2pb_pn2_three_interpolate       (PN2/interpolate_gpu.cu:84)
 //   p2pb_pn2_three_interpolate_grad  (PN2/interpolate_gpu.cu:127)
-// The caller owns every output; the gradient ADDS into its target. group_points* / gather_points* of the same extension
-// have the layout and arithmetic of p2pb_grouping_* / p2pb_gather_features_* (neighbors.hip, scatter_grad.hip) and are
-// routed there by the Python module. Squared distances are sqdist3 (common.h), as everywhere in the library.
+// The caller owns every output; the gradient ADDS into its target. p2pb_pn2_fps of the same extension is in fps_ref.hip,
+// with the pointops sampler it shares its kernels with; group_points* / gather_points* have the layout and arithmetic of
+// p2pb_grouping_* / p2pb_gather_features_* (neighbors.hip, scatter_grad.hip) and are routed there by the Python module.
+// Squared distances are sqdist3 (common.h), as everywhere in the library.
 #include "common.h"
-#include "fps_key.h"
 
 // ------------------------------------------------------------------------------------------------
 // ball query: one wave per centre, ballot + mbcnt ordered slots as ball_query_lds_kernel (neighbors.hip), the cloud
@@ -157,154 +156,6 @@ extern "C" int p2pb_pn2_three_nn(int b, int n, int m, const float *unknown, cons
   if (b <= 0 || b > 65535 || n <= 0 || m <= 0 || !unknown || !known || !dist2 || !idx) return P2PB_EINVAL;
   hipLaunchKernelGGL(pn2_three_nn_kernel, dim3(cdiv(n, 256), b), dim3(256), 0, (hipStream_t)stream, n, m, unknown, known,
                      dist2, idx);
-  return p2pb_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// furthest point sampling with the reference's contract: temp f32[B,N] is the caller's running minima, read on entry
-// (the layer fills it with 1e10) and written back once at the end, so it returns holding the minima over samples
-// 0 .. m-2 (the last pick starts no round).
-// Tie order: the reference's block has T(n) = min(2^floor(log2 n), 1024) threads (PN2/cuda_utils.h:10), thread t scans
-// k = t, t + T, ... keeping the first strict maximum, and its shared-memory tree keeps the lower thread on ties
-// (PN2/sampling_gpu.cu:93-98): (temp desc, k mod T asc, k asc). As in sampling.hip the order is the low word of a 64-bit
-// key, so any thread layout reproduces it; that file's key is fixed to the 512 threads of the PVCNN sampler, this one
-// takes log2 T.
-// One workgroup per cloud. n <= 16384: coordinates and minima in registers for the whole kernel, the winner's
-// coordinates from an LDS copy of the cloud when it fits; above: minima in temp itself, coordinates streamed from L2.
-// ------------------------------------------------------------------------------------------------
-// thread t owns k = t + i * THREADS. With PPT > 1 the launcher uses 1024 threads and n > 1024, so T = 1024: the thread's
-// points share k mod T and are visited in ascending k, and "first strict maximum" inside the thread is the tie order.
-template <int THREADS, int PPT, bool LDS_XYZ>
-__global__ __launch_bounds__(THREADS) void pn2_fps_kernel(int n, int m, int lt, const float *__restrict__ xyz,
-                                                          float *__restrict__ temp, int *__restrict__ idxs) {
-  extern __shared__ __attribute__((aligned(16))) char pn2_fps_smem[];
-  u64 *slots = (u64 *)pn2_fps_smem;                              // [2][16]
-  float *sxyz = (float *)(pn2_fps_smem + 2 * 16 * sizeof(u64));  // [n][3] when LDS_XYZ
-  const int t = threadIdx.x;
-  const float *c = xyz + (size_t)blockIdx.x * 3 * n;
-  float *tp = temp + (size_t)blockIdx.x * n;
-  int *out = idxs + (size_t)blockIdx.x * m;
-
-  float x[PPT], y[PPT], z[PPT], dist[PPT];
-#pragma unroll
-  for (int i = 0; i < PPT; ++i) {
-    const int k = t + i * THREADS;
-    const bool ok = k < n;
-    x[i] = ok ? c[3 * k] : 0.0f;
-    y[i] = ok ? c[3 * k + 1] : 0.0f;
-    z[i] = ok ? c[3 * k + 2] : 0.0f;
-    dist[i] = ok ? tp[k] : -1.0f;  // -1 = "no point here": stays -1, never selected
-  }
-  if (LDS_XYZ)
-    for (int k = t; k < 3 * n; k += THREADS) sxyz[k] = c[k];
-  if (t < 32) slots[t] = 0;
-  if (t == 0) out[0] = 0;
-  __syncthreads();
-
-  int old = 0;
-  for (int j = 1; j < m; ++j) {
-    float x1, y1, z1;
-    if (LDS_XYZ) {
-      x1 = sxyz[3 * old];
-      y1 = sxyz[3 * old + 1];
-      z1 = sxyz[3 * old + 2];
-    } else {
-      x1 = c[3 * old];
-      y1 = c[3 * old + 1];
-      z1 = c[3 * old + 2];
-    }
-    float best = -1.0f;
-    int bi = 0;
-#pragma unroll
-    for (int i = 0; i < PPT; ++i) {
-      const float d = sqdist3(x[i] - x1, y[i] - y1, z[i] - z1);
-      float d2;  // fminf(d, dist[i]) as the bare instruction (no canonicalising v_max_f32 in front: sampling.hip fps_kernel)
-      asm("v_min_f32 %0, %1, %2" : "=v"(d2) : "v"(d), "v"(dist[i]));
-      dist[i] = d2;
-      if (d2 > best) {
-        best = d2;
-        bi = i;
-      }
-    }
-    // (a thread without points offers the identity, not an index: whatever temp holds, the winner is a point of the cloud)
-    const int bk = t + bi * THREADS;
-    u64 key = pn2_max_u64<true>(bk < n ? pn2_fps_key(best, bk, lt) : 0);
-    if (THREADS > 64) key = pn2_block_max(key, slots, j, t);
-    old = pn2_fps_key_index(key, lt);
-    if (t == 0) out[j] = old;
-  }
-  if (m > 1) {
-#pragma unroll
-    for (int i = 0; i < PPT; ++i) {
-      const int k = t + i * THREADS;
-      if (k < n) tp[k] = dist[i];
-    }
-  }
-}
-
-// n > 16384 (T = 1024): the running minima live in temp, the cloud is streamed from L2 every round
-__global__ __launch_bounds__(1024) void pn2_fps_big_kernel(int n, int m, const float *__restrict__ xyz,
-                                                           float *__restrict__ temp, int *__restrict__ idxs) {
-  __shared__ u64 slots[2 * 16];
-  const int t = threadIdx.x;
-  const float *c = xyz + (size_t)blockIdx.x * 3 * n;
-  float *tp = temp + (size_t)blockIdx.x * n;
-  int *out = idxs + (size_t)blockIdx.x * m;
-  if (t < 32) slots[t] = 0;
-  if (t == 0) out[0] = 0;
-  __syncthreads();
-  int old = 0;
-  for (int j = 1; j < m; ++j) {
-    const float x1 = c[(size_t)3 * old], y1 = c[(size_t)3 * old + 1], z1 = c[(size_t)3 * old + 2];
-    float best = -1.0f;
-    int bk = 0;
-    for (int k = t; k < n; k += 1024) {
-      const float d = sqdist3(c[(size_t)3 * k] - x1, c[(size_t)3 * k + 1] - y1, c[(size_t)3 * k + 2] - z1);
-      const float d2 = fminf(d, tp[k]);
-      tp[k] = d2;
-      if (d2 > best) {
-        best = d2;
-        bk = k;
-      }
-    }
-    const u64 key = pn2_block_max(pn2_max_u64<true>(pn2_fps_key(best, bk, 10)), slots, j, t);
-    old = pn2_fps_key_index(key, 10);
-    if (t == 0) out[j] = old;
-  }
-}
-
-#define PN2_FPS_LDS_MAX (160 * 1024)
-template <int THREADS, int PPT>
-static void pn2_fps_launch(int b, int n, int m, int lt, const float *xyz, float *temp, int *idx, hipStream_t s) {
-  const size_t base = 2 * 16 * sizeof(u64), cloud = (size_t)3 * n * sizeof(float);
-  if (base + cloud <= PN2_FPS_LDS_MAX) {
-    static bool once = false;
-    if (!once) {
-      (void)hipFuncSetAttribute((const void *)pn2_fps_kernel<THREADS, PPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                PN2_FPS_LDS_MAX);
-      once = true;
-    }
-    hipLaunchKernelGGL((pn2_fps_kernel<THREADS, PPT, true>), dim3(b), dim3(THREADS), base + cloud, s, n, m, lt, xyz, temp, idx);
-  } else {
-    hipLaunchKernelGGL((pn2_fps_kernel<THREADS, PPT, false>), dim3(b), dim3(THREADS), base, s, n, m, lt, xyz, temp, idx);
-  }
-}
-
-extern "C" int p2pb_pn2_fps(int b, int n, int m, const float *xyz, float *temp, int *idx, void *stream) {
-  if (b <= 0 || n <= 0 || m < 0) return P2PB_EINVAL;
-  if (m == 0) return 0;  // (PN2/sampling_gpu.cu:108: nothing is written; idx i32[b,0] has no address)
-  if (!xyz || !temp || !idx) return P2PB_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  int lt = 0;  // log2 T(n)
-  while (lt < 10 && (2 << lt) <= n) ++lt;
-  if (n <= 64) pn2_fps_launch<64, 1>(b, n, m, lt, xyz, temp, idx, s);
-  else if (n <= 256) pn2_fps_launch<256, 1>(b, n, m, lt, xyz, temp, idx, s);
-  else if (n <= 1024) pn2_fps_launch<1024, 1>(b, n, m, lt, xyz, temp, idx, s);
-  else if (n <= 2048) pn2_fps_launch<1024, 2>(b, n, m, lt, xyz, temp, idx, s);
-  else if (n <= 4096) pn2_fps_launch<1024, 4>(b, n, m, lt, xyz, temp, idx, s);
-  else if (n <= 8192) pn2_fps_launch<1024, 8>(b, n, m, lt, xyz, temp, idx, s);
-  else if (n <= 16384) pn2_fps_launch<1024, 16>(b, n, m, lt, xyz, temp, idx, s);
-  else hipLaunchKernelGGL(pn2_fps_big_kernel, dim3(b), dim3(1024), 0, s, n, m, xyz, temp, idx);
   return p2pb_launch_status();
 }
 

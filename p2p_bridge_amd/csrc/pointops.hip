@@ -2,22 +2,19 @@
 // (PO = third_party/openpoints/cpp/pointops/src; include/p2pb_hip.h, section "packed-batch operators"):
 //   p2pb_pointops_knnquery            (PO/knnquery/knnquery_cuda_kernel.cu:65)
 //   p2pb_pointops_ballquery           (PO/ballquery/ballquery_cuda_kernel.cu:26)
-//   p2pb_pointops_furthestsampling    (PO/sampling/sampling_cuda_kernel.cu:15)
 //   p2pb_pointops_{grouping,interpolation,subtraction,aggregation}_{forward,backward}
-// One packed cloud xyz f32[n,3] with cumulative segment ends offset i32[b]; features point-major f32[n,c]. The caller owns
-// every output. Squared distances are sqdist3 (common.h) of query - point.
+// (p2pb_pointops_furthestsampling of the same extension is in fps_ref.hip, with the PointNet++ sampler it shares its kernels
+// with.) One packed cloud xyz f32[n,3] with cumulative segment ends offset i32[b]; features point-major f32[n,c]. The caller
+// owns every output. Squared distances are sqdist3 (common.h) of query - point.
 #include "common.h"
-#include "fps_key.h"
+#include "po_segment.h"
+
+typedef unsigned long long u64;  // the k-NN heap's keys
 
 // ------------------------------------------------------------------------------------------------
 // segments. Query i belongs to the first segment s with i < new_offset[s]; the search ends in [0, b-1] whatever the array
-// holds, ends are clamped to [0, n], an end below its start is an empty segment.
+// holds, ends are clamped to [0, n], an end below its start is an empty segment (po_segment.h).
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int po_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ void po_segment_points(int s, int n, const int *__restrict__ offset, int &start, int &end) {
-  start = s ? po_clamp(offset[s - 1], 0, n) : 0;
-  end = po_clamp(offset[s], start, n);
-}
 __device__ __forceinline__ int po_segment_of(int i, int b, const int *__restrict__ new_offset) {
   int lo = 0, hi = b - 1;
   while (lo < hi) {
@@ -213,157 +210,6 @@ extern "C" int p2pb_pointops_ballquery(int b, int n, int m, float radius, int ns
   const float r2 = radius * radius;  // the float product of PO/ballquery/ballquery_cuda_kernel.cu
   hipLaunchKernelGGL(po_ballquery_kernel, dim3(cdiv(m, 64)), dim3(64), 0, (hipStream_t)stream, b, n, m, r2, nsample, xyz,
                      new_xyz, offset, new_offset, idx);
-  return p2pb_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// furthest point sampling, one workgroup per segment, in the forms of pn2_fps_kernel (pointnet2_legacy.hip): a segment of
-// up to THREADS * PPT points keeps coordinates and running minima in registers (the winner's coordinates come from an LDS
-// copy of the segment when that fits), a longer one -- n_max > 16384, or a segment longer than n_max announced -- works in
-// tmp and streams its points from L2. The tie order is that of a block of T = 2^lt threads over the segment's LOCAL
-// indices (fps_key.h); the launcher takes T and the form from n_max, so PPT > 1 means T = THREADS = 1024 and a thread's
-// points share k mod T.
-// ------------------------------------------------------------------------------------------------
-template <int THREADS>
-__device__ __forceinline__ void po_fps_stream(int len, int ms, int lt, const float *__restrict__ c, float *__restrict__ tp,
-                                              int *__restrict__ out, int start_n, u64 *slots) {
-  const int t = threadIdx.x;
-  int old = 0;
-  for (int j = 1; j < ms; ++j) {
-    const float x1 = c[(size_t)3 * old], y1 = c[(size_t)3 * old + 1], z1 = c[(size_t)3 * old + 2];
-    float best = -1.0f;
-    int bk = t;
-    for (int k = t; k < len; k += THREADS) {  // (THREADS is a multiple of T: the thread's points share k mod T)
-      const float d = sqdist3(c[(size_t)3 * k] - x1, c[(size_t)3 * k + 1] - y1, c[(size_t)3 * k + 2] - z1);
-      const float d2 = fminf(d, tp[k]);
-      tp[k] = d2;
-      if (d2 > best) {
-        best = d2;
-        bk = k;
-      }
-    }
-    u64 key = pn2_max_u64<true>(bk < len ? pn2_fps_key(best, bk, lt) : 0);
-    if (THREADS > 64) key = pn2_block_max(key, slots, j, t);
-    old = pn2_fps_key_index(key, lt);
-    if (t == 0) out[j] = start_n + old;
-  }
-}
-
-template <int THREADS, int PPT, bool LDS_XYZ>  // PPT == 0: the streaming form only
-__global__ __launch_bounds__(THREADS) void po_fps_kernel(int n, int m, int lt, const float *__restrict__ xyz,
-                                                         const int *__restrict__ offset,
-                                                         const int *__restrict__ new_offset, float *__restrict__ tmp,
-                                                         int *__restrict__ idx) {
-  extern __shared__ __attribute__((aligned(16))) char po_fps_smem[];
-  u64 *slots = (u64 *)po_fps_smem;                              // [2][16]
-  float *sxyz = (float *)(po_fps_smem + 2 * 16 * sizeof(u64));  // [THREADS * PPT][3] when LDS_XYZ
-  const int t = threadIdx.x, s = blockIdx.x;
-  int start_n, end_n;
-  po_segment_points(s, n, offset, start_n, end_n);
-  const int start_m = s ? po_clamp(new_offset[s - 1], 0, m) : 0;
-  const int ms = po_clamp(new_offset[s], start_m, m) - start_m;
-  const int len = end_n - start_n;
-  if (len == 0 || ms == 0) return;  // (the whole workgroup)
-  const float *c = xyz + (size_t)3 * start_n;
-  float *tp = tmp + start_n;
-  int *out = idx + start_m;
-  if (t < 32) slots[t] = 0;
-  if (t == 0) out[0] = start_n;
-  if constexpr (PPT == 0) {
-    __syncthreads();
-    po_fps_stream<THREADS>(len, ms, lt, c, tp, out, start_n, slots);
-  } else {
-    if (len > THREADS * PPT) {
-      __syncthreads();
-      po_fps_stream<THREADS>(len, ms, lt, c, tp, out, start_n, slots);
-      return;
-    }
-    float x[PPT], y[PPT], z[PPT], dist[PPT];
-#pragma unroll
-    for (int i = 0; i < PPT; ++i) {
-      const int k = t + i * THREADS;
-      const bool ok = k < len;
-      x[i] = ok ? c[3 * k] : 0.0f;
-      y[i] = ok ? c[3 * k + 1] : 0.0f;
-      z[i] = ok ? c[3 * k + 2] : 0.0f;
-      dist[i] = ok ? tp[k] : -1.0f;  // -1 = "no point here": stays -1, never selected
-    }
-    if (LDS_XYZ)
-      for (int k = t; k < 3 * len; k += THREADS) sxyz[k] = c[k];
-    __syncthreads();
-
-    int old = 0;
-    for (int j = 1; j < ms; ++j) {
-      float x1, y1, z1;
-      if (LDS_XYZ) {
-        x1 = sxyz[3 * old];
-        y1 = sxyz[3 * old + 1];
-        z1 = sxyz[3 * old + 2];
-      } else {
-        x1 = c[3 * old];
-        y1 = c[3 * old + 1];
-        z1 = c[3 * old + 2];
-      }
-      float best = -1.0f;
-      int bi = 0;
-#pragma unroll
-      for (int i = 0; i < PPT; ++i) {
-        const float d2 = vmin_raw(sqdist3(x[i] - x1, y[i] - y1, z[i] - z1), dist[i]);
-        dist[i] = d2;
-        if (d2 > best) {
-          best = d2;
-          bi = i;
-        }
-      }
-      const int bk = t + bi * THREADS;
-      u64 key = pn2_max_u64<true>(bk < len ? pn2_fps_key(best, bk, lt) : 0);
-      if (THREADS > 64) key = pn2_block_max(key, slots, j, t);
-      old = pn2_fps_key_index(key, lt);
-      if (t == 0) out[j] = start_n + old;
-    }
-    if (ms > 1) {
-#pragma unroll
-      for (int i = 0; i < PPT; ++i) {
-        const int k = t + i * THREADS;
-        if (k < len) tp[k] = dist[i];
-      }
-    }
-  }
-}
-
-#define PO_FPS_LDS_MAX (160 * 1024)
-template <int THREADS, int PPT>
-static void po_fps_launch(int b, int n, int m, int lt, const float *xyz, const int *offset, const int *new_offset, float *tmp,
-                          int *idx, hipStream_t s) {
-  constexpr size_t base = 2 * 16 * sizeof(u64), cloud = (size_t)3 * THREADS * PPT * sizeof(float);
-  if constexpr (PPT > 0 && base + cloud <= PO_FPS_LDS_MAX) {
-    // (on every launch: the attribute belongs to the current device, and the call is cheap)
-    (void)hipFuncSetAttribute((const void *)po_fps_kernel<THREADS, PPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              PO_FPS_LDS_MAX);
-    hipLaunchKernelGGL((po_fps_kernel<THREADS, PPT, true>), dim3(b), dim3(THREADS), base + cloud, s, n, m, lt, xyz, offset,
-                       new_offset, tmp, idx);
-  } else {
-    hipLaunchKernelGGL((po_fps_kernel<THREADS, PPT, false>), dim3(b), dim3(THREADS), base, s, n, m, lt, xyz, offset,
-                       new_offset, tmp, idx);
-  }
-}
-
-extern "C" int p2pb_pointops_furthestsampling(int b, int n, int m, int n_max, const float *xyz, const int *offset,
-                                              const int *new_offset, float *tmp, int *idx, void *stream) {
-  if (b < 0 || n < 0 || m < 0) return P2PB_EINVAL;
-  if (b == 0 || n == 0 || m == 0) return 0;
-  if (n_max < 1 || !xyz || !offset || !new_offset || !tmp || !idx) return P2PB_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  int lt = 0;  // log2 T(n_max)
-  while (lt < 10 && (2 << lt) <= n_max) ++lt;
-  if (n_max <= 64) po_fps_launch<64, 1>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else if (n_max <= 256) po_fps_launch<256, 1>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else if (n_max <= 1024) po_fps_launch<1024, 1>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else if (n_max <= 2048) po_fps_launch<1024, 2>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else if (n_max <= 4096) po_fps_launch<1024, 4>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else if (n_max <= 8192) po_fps_launch<1024, 8>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else if (n_max <= 16384) po_fps_launch<1024, 16>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
-  else po_fps_launch<1024, 0>(b, n, m, lt, xyz, offset, new_offset, tmp, idx, s);
   return p2pb_launch_status();
 }
 

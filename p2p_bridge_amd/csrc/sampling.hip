@@ -14,61 +14,8 @@
 // net order is (d desc, k mod 512 asc, k asc); it is encoded in the low word of the key so any
 // thread layout reproduces it.
 #include "common.h"
+#include "fps_key.h"
 #include <cstdlib>
-
-typedef unsigned long long u64;
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_umax_step(unsigned v) {
-  const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);  // (0 = identity of max)
-  return o > v ? o : v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-  v = dpp_umax_step<0x111, 0xf>(v);  // row_shr:1
-  v = dpp_umax_step<0x112, 0xf>(v);  // row_shr:2
-  v = dpp_umax_step<0x114, 0xf>(v);  // row_shr:4
-  v = dpp_umax_step<0x118, 0xf>(v);  // row_shr:8   -> lane 15 of every row holds the row max
-  v = dpp_umax_step<0x142, 0xa>(v);  // row_bcast:15 into rows 1,3
-  v = dpp_umax_step<0x143, 0xc>(v);  // row_bcast:31 into rows 2,3 -> lane 63 holds the wave max
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-// max of 64-bit keys over the 64 lanes, broadcast to all lanes: the lexicographic maximum as two 32-bit reductions (the high
-// words, then the low words of the lanes that hold the winning high word) -- v_max_u32 steps instead of 64-bit compare +
-// two selects per step (the round of the small-cloud FPS is bound by its VALU instruction count)
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-  const unsigned hi = (unsigned)(v >> 32);
-  const unsigned H = wave_max_u32(hi);
-  const unsigned L = wave_max_u32(hi == H ? (unsigned)v : 0u);
-  return ((u64)H << 32) | L;
-}
-
-// max over the first 16-lane row of the wave, returned in every lane (the callers' rows all hold the same 16 values): the same
-// two 32-bit reductions
-__device__ __forceinline__ unsigned row_max_u32(unsigned v) {
-  v = dpp_umax_step<0x111, 0xf>(v);
-  v = dpp_umax_step<0x112, 0xf>(v);
-  v = dpp_umax_step<0x114, 0xf>(v);
-  v = dpp_umax_step<0x118, 0xf>(v);
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 15);
-}
-__device__ __forceinline__ u64 row_max_u64(u64 v) {
-  const unsigned hi = (unsigned)(v >> 32);
-  const unsigned H = row_max_u32(hi);
-  const unsigned L = row_max_u32(hi == H ? (unsigned)v : 0u);
-  return ((u64)H << 32) | L;
-}
-
-__device__ __forceinline__ u64 fps_key(float best, int k) {
-  // best >= 0 for any real point; threads without points carry best = -1 -> lowest key
-  const unsigned hi = best >= 0.0f ? (__float_as_uint(best) + 1u) : 0u;
-  const unsigned sec = ((unsigned)(k & 511) << 20) | (unsigned)(k >> 9);  // lower is better
-  return ((u64)hi << 32) | (u64)(~sec);
-}
-
-__device__ __forceinline__ int fps_key_index(u64 key) {
-  const unsigned sec = ~(unsigned)key;
-  return (int)(((sec & 0xFFFFFu) << 9) | (sec >> 20));
-}
 
 // Point index owned by (thread t, slot i). A thread must visit its points in ascending
 // (k mod 512, k) so that "first strict maximum" inside the thread agrees with the global tie order.
@@ -137,13 +84,13 @@ __global__ __launch_bounds__(THREADS) void fps_kernel(int n, int m, const float 
         bi = i;
       }
     }
-    u64 key = wave_max_u64(fps_key(best, fps_point<THREADS, PPT>(t, bi)));
+    u64 key = max_u64<true>(fps_key(best, fps_point<THREADS, PPT>(t, bi)));
     if (NW > 1) {
       u64 *sl = slots + (j & 1) * 16;
       if ((t & 63) == 0) sl[t >> 6] = key;
       __syncthreads();
       u64 v = sl[t & 15];  // entries >= NW stay 0 (identity)
-      v = row_max_u64(v);
+      v = max_u64<false>(v);
       const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 15);
       const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 15);
       key = ((u64)hi << 32) | lo;
@@ -182,10 +129,10 @@ __global__ __launch_bounds__(1024) void fps_big_kernel(int n, int m, const float
         bk = k;
       }
     }
-    u64 key = wave_max_u64(fps_key(best, bk));
+    u64 key = max_u64<true>(fps_key(best, bk));
     if ((t & 63) == 0) slots[j & 1][t >> 6] = key;
     __syncthreads();
-    u64 v = row_max_u64(slots[j & 1][t & 15]);
+    u64 v = max_u64<false>(slots[j & 1][t & 15]);
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 15);
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 15);
     old = fps_key_index(((u64)hi << 32) | lo);
@@ -258,11 +205,11 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int n, int m, const floa
         bk = g * 1024 + t + i * (FPS_G * 1024);
       }
     }
-    u64 key = wave_max_u64(fps_key(best, bk));
+    u64 key = max_u64<true>(fps_key(best, bk));
     if ((t & 63) == 0) slots[j & 1][t >> 6] = key;
     __syncthreads();
     if (t < 64) {  // wave 0: the workgroup's maximum -> its global word, then gather everybody's
-      u64 v = row_max_u64(slots[j & 1][t & 15]);
+      u64 v = max_u64<false>(slots[j & 1][t & 15]);
       const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 15);
       const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 15);
       const int par = (j & 1) * FPS_G;
@@ -280,7 +227,7 @@ __global__ __launch_bounds__(1024) void fps_coop_kernel(int n, int m, const floa
         }
         __builtin_amdgcn_s_sleep(1);
       }
-      const u64 all = wave_max_u64(fps_untag(w));
+      const u64 all = max_u64<true>(fps_untag(w));
       const bool lost = __ballot(spins < 0) != 0;
       if (t == 0) winner[j & 1] = lost ? -1 : fps_key_index(all);
     }
@@ -615,7 +562,7 @@ __global__ __launch_bounds__(1024) void fps_grid_kernel(int n, int m, const floa
             }
           }
         }
-        const u64 wbest = wave_max_u64(best);
+        const u64 wbest = max_u64<true>(best);
         const int from = __builtin_ctzll(__ballot(best == wbest));  // (keys are unique: the point index is part of them)
         const float wx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, bxv), from));
         const float wy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, byv), from));
@@ -636,7 +583,7 @@ __global__ __launch_bounds__(1024) void fps_grid_kernel(int n, int m, const floa
         key = ckey[i];
         kx = cx[i], ky = cy[i], kz = cz[i];
       }
-    const u64 wkey = wave_max_u64(key);
+    const u64 wkey = max_u64<true>(key);
     if (key == wkey && (wkey != 0 ? true : lane == 0)) {  // (an all-empty wave: lane 0 writes the zero key)
       slots[j & 1][wave] = wkey;
       // (one 16-byte store: three adjacent floats become a ds_write_b96, which misbehaved beside another stream's matrix
@@ -645,7 +592,7 @@ __global__ __launch_bounds__(1024) void fps_grid_kernel(int n, int m, const floa
     }
     __syncthreads();
     const u64 mine = slots[j & 1][t & 15];
-    const u64 v = row_max_u64(mine);
+    const u64 v = max_u64<false>(mine);
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 15);
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 15);
     const u64 fin = ((u64)hi << 32) | lo;

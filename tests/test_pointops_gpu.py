@@ -256,6 +256,11 @@ FPS_CASES = {
     "A-first-none": ([300, 1, 699], [0, 3, 150], [699]),
     "B": ([4100, 37], [130, 5], [4100, 2500, 37]),
     "big": ([17000, 50], [12, 60], [17000]),
+    # segments longer than n_max announces that still fit the points-per-thread form n_max chooses (1500: two per thread, up
+    # to 2048; 9000: sixteen, up to 16384), where the LDS copy of the winner's coordinates is sized by n_max; each next to the
+    # n_max that tells the truth, and 16384: the sixteen-per-thread form without the copy
+    "C": ([2000, 50], [64, 20], [1500, 2000]),
+    "D": ([12000, 300], [64, 32], [9000, 12000, 16384]),
 }
 
 
@@ -284,6 +289,25 @@ def test_furthestsampling_ties_are_common_in_the_exact_fixture():
         tied += top.size > 1
         last = top[np.lexsort((top, top % 512))[0]]
     assert tied >= 10, tied
+
+
+@pytest.mark.parametrize("n", [37, 1000, 2500, 9000, 16000, 20000])
+def test_furthestsampling_is_the_batched_sampler_on_equal_segments(ext, n):
+    """`pointnet2_batch_cuda.furthest_point_sampling_wrapper` on [b, n, 3] and `furthestsampling_cuda` on the same clouds
+    packed with n_max = n run one kernel family: equal indices once a segment's start is taken off, equal running minima.
+    n: 64 threads; 1024 with one and four points each; sixteen with and without the LDS copy; the streaming form."""
+    from p2p_bridge_amd import pointnet2_batch_cuda
+
+    b, m = 2, min(n, 64)
+    xyz = dev(cloud(np.random.default_rng(11).integers(-8, 9, (b, n, 3))))
+    temp = torch.full((b, n), 1e10, dtype=F32, device="cuda")
+    bidx = torch.full((b, m), -7, dtype=I32, device="cuda")
+    assert pointnet2_batch_cuda.furthest_point_sampling_wrapper(b, n, m, xyz, temp, bidx) == 1
+    sh = Shape([n] * b, [m] * b)
+    pidx, tmp = run_fps(ext, sh, xyz.reshape(b * n, 3).cpu().numpy(), n)
+    starts = torch.arange(b, dtype=I32, device="cuda")[:, None] * n
+    same_bits(pidx.reshape(b, m) - starts, bidx.cpu().numpy(), f"packed against batched idx, n = {n}")
+    same_bits(tmp.reshape(b, n), temp.cpu().numpy(), f"packed against batched tmp, n = {n}")
 
 
 # ---- the exact family: arithmetic -----------------------------------------------------------------------------------------

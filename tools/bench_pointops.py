@@ -1,5 +1,5 @@
-"""Times the three search kernels of csrc/pointops.hip at a Point-Transformer-like shape through the `*_cuda` functions of
-p2p_bridge_amd/pointops_cuda.py: b = 4 equal segments, uniform fp32 clouds in [-1, 1]^3,
+"""Times the three search operators of the pointops extension (csrc/pointops.hip; furthestsampling: csrc/fps_ref.hip) at a
+Point-Transformer-like shape through the `*_cuda` functions of p2p_bridge_amd/pointops_cuda.py: b = 4 equal segments, uniform fp32 clouds in [-1, 1]^3,
   knnquery           n = m = 40960 (the cloud queries itself), nsample 16
   ballquery          the same shape, radius 0.1
   furthestsampling   40960 -> 10240
