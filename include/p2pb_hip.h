@@ -202,7 +202,7 @@ int p2pb_three_nn_interpolate_backward(int b, int c, int n, int m, const float *
 int p2pb_three_nn_interpolate_backward_pitched(int b, int c, int n, int m, const float *grad_y, long gy_pitch, const int *idx,
                                                const float *w, float *grad_x, void *stream);
 
-/* ---- the classic PointNet++ operators of the same extension (csrc/pointnet2_legacy.hip; FPS: csrc/fps_ref.hip) -------
+/* ---- the classic PointNet++ operators of the same extension (csrc/ball_query.hip, three_nn.hip; FPS: fps_ref.hip) ----
  * Replace the launchers behind ball_query_wrapper, three_nn_wrapper, furthest_point_sampling_wrapper,
  * three_interpolate_wrapper and three_interpolate_grad_wrapper (PN2/pointnet2_api.cpp:17-29; kernels PN2/ball_query_gpu.cu:15,
  * interpolate_gpu.cu:16,84,127, sampling_gpu.cu:101). Clouds are POINT-major f32[b,n,3], features channel-major; argument

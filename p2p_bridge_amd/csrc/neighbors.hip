@@ -1,138 +1,12 @@
-// neighbors.hip -- neighbourhood search / gather kernels for gfx950.
-//   p2pb_ball_query                  (PN2/pvcnn_ball_query_gpu.cu:19)
+// neighbors.hip -- grouping / gather kernels of the set abstraction and feature propagation for gfx950.
 //   p2pb_grouping_forward            (PN2/pvcnn_grouping_gpu.cu:18)
 //   p2pb_gather_features_forward     (PN2/pvcnn_sampling_gpu.cu:17)
-//   p2pb_three_nn_interpolate_forward (PN2/pvcnn_neighbor_interpolate_gpu.cu:20,96)
-// (their backward passes: scatter_grad.hip)
+//   p2pb_group_concat, p2pb_group_sub, p2pb_group_sub_stats, p2pb_three_interpolate_add: the fused forms of the sampler
+// (their backward passes: scatter_grad.hip; the searches that produce the indices: ball_query.hip, three_nn.hip, which also
+// holds the plain three-interpolate)
 // The reference runs ONE thread block per cloud for each of these; here every kernel is spread over
 // (points or centres) x channels x batch so a B=32 launch covers all 256 CUs.
 #include "common.h"
-
-// ------------------------------------------------------------------------------------------------
-// ball query: one 64-lane wave per centre. The wave streams the cloud 64 points at a time
-// (lane-consecutive = coalesced reads of the [3,N] coordinate rows), a wave ballot marks the
-// in-radius lanes and the popcount of the lower lanes is the output slot, which reproduces the
-// reference's "first u hits in ascending point index" order exactly; the scan stops as soon as
-// u hits are found.
-// ------------------------------------------------------------------------------------------------
-template <int UNROLL>
-__global__ __launch_bounds__(256) void ball_query_kernel(int n, int m, float r2, int u,
-                                                         const float *__restrict__ centers,
-                                                         const float *__restrict__ points, int *__restrict__ idx) {
-  const int b = blockIdx.y;
-  const int lane = lane_id();
-  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (j >= m) return;
-  const float *p = points + (size_t)b * 3 * n;
-  const float *ce = centers + (size_t)b * 3 * m;
-  int *o = idx + ((size_t)b * m + j) * u;
-  const float cx = ce[j], cy = ce[j + m], cz = ce[j + 2 * m];
-  int cnt = 0, first = 0;
-  for (int base = 0; base < n && cnt < u; base += 64 * UNROLL) {
-    float px[UNROLL], py[UNROLL], pz[UNROLL];
-#pragma unroll
-    for (int q = 0; q < UNROLL; ++q) {
-      const int k = base + q * 64 + lane;
-      const bool ok = k < n;
-      px[q] = ok ? p[k] : 0.0f;
-      py[q] = ok ? p[k + n] : 0.0f;
-      pz[q] = ok ? p[k + 2 * n] : 0.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < UNROLL; ++q) {
-      const int k = base + q * 64 + lane;
-      const float d2 = sqdist3(cx - px[q], cy - py[q], cz - pz[q]);
-      const bool in = (k < n) && (d2 < r2);
-      const unsigned long long mask = __ballot(in);
-      if (mask) {
-        const int slot = cnt + mbcnt(mask);
-        if (in && slot < u) o[slot] = k;
-        if (cnt == 0) first = base + q * 64 + (int)__builtin_ctzll(mask);
-        cnt += (int)__builtin_popcountll(mask);
-      }
-    }
-  }
-  // PN2/pvcnn_ball_query_gpu.cu:44-50: on the first hit every slot is set to it; later hits
-  // overwrite slots 0..cnt-1. No hit at all leaves the zero initialisation (pvcnn_ball_query.cpp:21).
-  for (int v = lane; v < u; v += 64)
-    if (v >= cnt) o[v] = cnt > 0 ? first : 0;
-}
-
-// The same scan with the cloud in LDS. One wave per centre straight from global memory makes every wave re-read the
-// cloud through L1/L2: 2048 centres x ~48 % of 8192 points x 12 B x 32 samples = 3 GB of cache traffic per call at the
-// first level. Alone the kernel is bound by instruction issue either way (190 us: ~25 instructions per 64-point step,
-// mostly the ballot / slot bookkeeping -- packed fp32 for the distances changes nothing), but it runs on the geometry
-// stream BESIDE the GEMMs and convolutions of the main stream, which need that cache bandwidth: with a workgroup of
-// 16 waves copying the cloud into LDS once (3 x n floats, 96 KB at n = 8192) and every wave walking `cpw` centres over
-// it, the sampler gains 0.9 % end to end. Same hit order, same outputs.
-template <int UNROLL>
-__global__ __launch_bounds__(1024) void ball_query_lds_kernel(int n, int m, float r2, int u, int cpw,
-                                                              const float *__restrict__ centers,
-                                                              const float *__restrict__ points,
-                                                              int *__restrict__ idx) {
-  extern __shared__ float bq_pts[];  // [3][n]
-  const int b = blockIdx.y;
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  const float *p = points + (size_t)b * 3 * n;
-  const float *ce = centers + (size_t)b * 3 * m;
-  for (int k = threadIdx.x; k < 3 * n; k += 1024) bq_pts[k] = p[k];
-  __syncthreads();
-  const float *sx = bq_pts, *sy = bq_pts + n, *sz = bq_pts + 2 * n;
-  const int j0 = (blockIdx.x * 16 + wave) * cpw;
-  for (int j = j0; j < min(j0 + cpw, m); ++j) {
-    int *o = idx + ((size_t)b * m + j) * u;
-    const float cx = ce[j], cy = ce[j + m], cz = ce[j + 2 * m];
-    int cnt = 0, first = 0;
-    for (int base = 0; base < n && cnt < u; base += 64 * UNROLL) {
-      float px[UNROLL], py[UNROLL], pz[UNROLL];
-#pragma unroll
-      for (int q = 0; q < UNROLL; ++q) {
-        const int k = min(base + q * 64 + lane, n - 1);
-        px[q] = sx[k];
-        py[q] = sy[k];
-        pz[q] = sz[k];
-      }
-#pragma unroll
-      for (int q = 0; q < UNROLL; ++q) {
-        const int k = base + q * 64 + lane;
-        const float d2 = sqdist3(cx - px[q], cy - py[q], cz - pz[q]);
-        const bool in = (k < n) && (d2 < r2);
-        const unsigned long long mask = __ballot(in);
-        if (mask) {
-          const int slot = cnt + mbcnt(mask);
-          if (in && slot < u) o[slot] = k;
-          if (cnt == 0) first = base + q * 64 + (int)__builtin_ctzll(mask);
-          cnt += (int)__builtin_popcountll(mask);
-        }
-      }
-    }
-    for (int v = lane; v < u; v += 64)
-      if (v >= cnt) o[v] = cnt > 0 ? first : 0;
-  }
-}
-
-extern "C" int p2pb_ball_query(int b, int n, int m, float r2, int u, const float *centers, const float *points,
-                               int *idx, void *stream) {
-  if (b <= 0 || n <= 0 || m <= 0 || u <= 0) return P2PB_EINVAL;
-  const size_t lds = (size_t)3 * n * sizeof(float);
-  if (lds <= 144 * 1024 && (long)m * b >= 2048) {  // the cloud fits in LDS and there are enough centres to share it
-    static bool once = false;
-    if (!once) {
-      (void)hipFuncSetAttribute((const void *)ball_query_lds_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
-      once = true;
-    }
-    // centres per wave: about two workgroups per CU over the whole launch, at least 1
-    int cpw = (int)(((long)m * b + 16L * 512 - 1) / (16L * 512));
-    if (cpw < 1) cpw = 1;
-    hipLaunchKernelGGL(ball_query_lds_kernel<4>, dim3(cdiv(m, 16 * cpw), b), dim3(1024), lds, (hipStream_t)stream, n, m,
-                       r2, u, cpw, centers, points, idx);
-    return p2pb_launch_status();
-  }
-  hipLaunchKernelGGL(ball_query_kernel<4>, dim3(cdiv(m, 4), b), dim3(256), 0, (hipStream_t)stream, n, m, r2, u,
-                     centers, points, idx);
-  return p2pb_launch_status();
-}
 
 // ------------------------------------------------------------------------------------------------
 // grouping: out[b,c,j,k] = feat[b,c,idx[b,j,k]] . One thread per (j,k) slot, looping a chunk of
@@ -429,373 +303,6 @@ extern "C" int p2pb_gather_features_forward(int b, int c, int n, int m, const fl
   if (b <= 0 || c <= 0 || n <= 0 || m <= 0) return P2PB_EINVAL;
   hipLaunchKernelGGL(gather_kernel, dim3(cdiv(m, 256), c, b), dim3(256), 0, (hipStream_t)stream, c, n, m, feat, idx,
                      out);
-  return p2pb_launch_status();
-}
-
-// ------------------------------------------------------------------------------------------------
-// three nearest centres + inverse-squared-distance weights: one thread per point, the centre
-// coordinates are staged through LDS in tiles and read back as wave-wide broadcasts.
-// The reference keeps its three bests as doubles initialised to 1e40 (never reached by an fp32
-// distance); +inf in fp32 takes exactly the same branches and clamps to the same 1e10f.
-// ------------------------------------------------------------------------------------------------
-#define NN_TILE 2048
-__global__ __launch_bounds__(256) void three_nn_kernel(int n, int m, const float *__restrict__ points,
-                                                       const float *__restrict__ centers, float *__restrict__ weights,
-                                                       int *__restrict__ indices) {
-  __shared__ float sc[3][NN_TILE];
-  const int b = blockIdx.y;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  const float *p = points + (size_t)b * 3 * n;
-  const float *ce = centers + (size_t)b * 3 * m;
-  const bool ok = j < n;
-  const float ux = ok ? p[j] : 0.0f, uy = ok ? p[j + n] : 0.0f, uz = ok ? p[j + 2 * n] : 0.0f;
-  float best0 = INFINITY, best1 = INFINITY, best2 = INFINITY;
-  int i0 = 0, i1 = 0, i2 = 0;
-  for (int k0 = 0; k0 < m; k0 += NN_TILE) {
-    const int kn = min(NN_TILE, m - k0);
-    __syncthreads();
-    for (int k = threadIdx.x; k < kn; k += 256) {
-      sc[0][k] = ce[k0 + k];
-      sc[1][k] = ce[k0 + k + m];
-      sc[2][k] = ce[k0 + k + 2 * m];
-    }
-    __syncthreads();
-    auto insert = [&](float d, int k) {
-      if (d < best2) {
-        best2 = d;
-        i2 = k;
-        if (d < best1) {
-          best2 = best1;
-          i2 = i1;
-          best1 = d;
-          i1 = k;
-          if (d < best0) {
-            best1 = best0;
-            i1 = i0;
-            best0 = d;
-            i0 = k;
-          }
-        }
-      }
-    };
-    for (int k = 0; k < kn; ++k) insert(sqdist3(ux - sc[0][k], uy - sc[1][k], uz - sc[2][k]), k0 + k);
-  }
-  if (!ok) return;
-  best0 = fmaxf(fminf(1e10f, best0), 1e-10f);
-  best1 = fmaxf(fminf(1e10f, best1), 1e-10f);
-  best2 = fmaxf(fminf(1e10f, best2), 1e-10f);
-  const float d0d1 = best0 * best1, d0d2 = best0 * best2, d1d2 = best1 * best2;
-  const float inv = __fdiv_rn(1.0f, d0d1 + d0d2 + d1d2);
-  float *w = weights + (size_t)b * 3 * n;
-  int *id = indices + (size_t)b * 3 * n;
-  w[j] = d1d2 * inv;
-  id[j] = i0;
-  w[j + n] = d0d2 * inv;
-  id[j + n] = i1;
-  w[j + 2 * n] = d0d1 * inv;
-  id[j + 2 * n] = i2;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same search through a uniform grid over the centres (exact): brute force evaluates n x m pairs (537 M per call
-// at the first level; ~190 us of pure instruction issue, more beside the main stream), the grid ~50 per point.
-//   nn_cells_build : one workgroup per cloud. Cubic cells of edge h = (largest bounding-box extent of the centres) /
-//                    NNC_G; count (LDS atomics) -> exclusive scan -> fill -> every cell's short id list sorted
-//                    ascending. cell_start i32[b][G^3 + 1], cell_ids i32[b][m], box f32[b][4] = (min x, y, z, h).
-//   three_nn_cells : one thread per point, the cloud's records + cell table in LDS: visit the cells within Chebyshev
-//                    radius rho of the point's (clamped) cell, rho = 1 (the 3x3x3 block), 2, ... (one more shell
-//                    each); every centre outside is farther than rho * h, so the search stops as
-//                    soon as three are held and the third distance is <= (rho h)^2. Candidates arrive out of index
-//                    order, so ties are broken explicitly (smaller index first) -- what "first strict minimum in
-//                    ascending index" gives the brute-force kernel. Same distances (sqdist3), same weights.
-// ------------------------------------------------------------------------------------------------
-#define NNC_G 16
-#define NNC_CELLS (NNC_G * NNC_G * NNC_G)
-
-__global__ __launch_bounds__(1024) void nn_cells_build_kernel(int m, const float *__restrict__ centers,
-                                                              int *__restrict__ cell_start, int *__restrict__ cell_ids,
-                                                              float4 *__restrict__ cell_rec, float *__restrict__ box) {
-  __shared__ int cnt[NNC_CELLS];
-  __shared__ int part[1024];
-  __shared__ float red[6][16];
-  __shared__ float sbox[4];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const float *ce = centers + (size_t)b * 3 * m;
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int k = t; k < m; k += 1024)
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float v = ce[k + a * m];
-      lo[a] = fminf(lo[a], v);
-      hi[a] = fmaxf(hi[a], v);
-    }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], o));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o));
-    }
-    if (lane == 0) {
-      red[a][wave] = lo[a];
-      red[3 + a][wave] = hi[a];
-    }
-  }
-  for (int i = t; i < NNC_CELLS; i += 1024) cnt[i] = 0;
-  __syncthreads();
-  if (t == 0) {
-    float mn[3], ext = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-      float l = INFINITY, h = -INFINITY;
-      for (int w = 0; w < 16; ++w) {
-        l = fminf(l, red[a][w]);
-        h = fmaxf(h, red[3 + a][w]);
-      }
-      mn[a] = l;
-      ext = fmaxf(ext, h - l);
-    }
-    const float hcell = fmaxf(ext, 1e-12f) / NNC_G;
-    for (int a = 0; a < 3; ++a) {
-      sbox[a] = mn[a];
-      box[(size_t)b * 4 + a] = mn[a];
-    }
-    sbox[3] = hcell;
-    box[(size_t)b * 4 + 3] = hcell;
-  }
-  __syncthreads();
-  const float inv = 1.0f / sbox[3];
-  auto cell_of = [&](int k) {
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = min(max((int)floorf((ce[k + a * m] - sbox[a]) * inv), 0), NNC_G - 1);
-    return (c[2] * NNC_G + c[1]) * NNC_G + c[0];
-  };
-  for (int k = t; k < m; k += 1024) atomicAdd(&cnt[cell_of(k)], 1);
-  __syncthreads();
-  // exclusive scan of the 4096 counts: thread t owns cells 4t .. 4t+3
-  int c4[4], tot = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    c4[i] = cnt[4 * t + i];
-    tot += c4[i];
-  }
-  part[t] = tot;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
-  int run = part[t] - tot;
-  int *cs = cell_start + (size_t)b * (NNC_CELLS + 1);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    cs[4 * t + i] = run;
-    cnt[4 * t + i] = run;  // becomes the fill cursor
-    run += c4[i];
-  }
-  if (t == 1023) cs[NNC_CELLS] = run;
-  __syncthreads();
-  int *ids = cell_ids + (size_t)b * m;
-  for (int k = t; k < m; k += 1024) ids[atomicAdd(&cnt[cell_of(k)], 1)] = k;
-  __syncthreads();
-  // ascending ids inside every cell (insertion sort of a short list by the cell's owner thread)
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int s0 = cs[4 * t + i], s1 = s0 + c4[i];
-    for (int x = s0 + 1; x < s1; ++x) {
-      const int v = ids[x];
-      int y = x - 1;
-      while (y >= s0 && ids[y] > v) {
-        ids[y + 1] = ids[y];
-        --y;
-      }
-      ids[y + 1] = v;
-    }
-    // the cell's centres as (x, y, z, id) records, contiguous: what the search streams through LDS
-    float4 *rec = cell_rec + (size_t)b * m;
-    for (int x = s0; x < s1; ++x) {
-      const int k = ids[x];
-      rec[x] = make_float4(ce[k], ce[k + m], ce[k + 2 * m], __int_as_float(k));
-    }
-  }
-}
-
-template <bool LDS_REC>  // false (m > NNC_MAX_M, PVDL's 12500-centre level): the records stay in global memory (L2-resident:
-                         // 16 m bytes per cloud), only the cell table goes to LDS -- many workgroups per CU hide the L2 trips
-__global__ __launch_bounds__(256) void three_nn_cells_kernel(int n, int m, const float *__restrict__ points,
-                                                             const int *__restrict__ cell_start,
-                                                             const float4 *__restrict__ cell_rec,
-                                                             const float *__restrict__ box, float *__restrict__ weights,
-                                                             int *__restrict__ indices) {
-  // the cloud's cell table and sorted centre records, shared by the workgroup's 256 points (all of one cloud):
-  // every candidate is then one 16-byte LDS read at an address known up front (no dependent global loads)
-  extern __shared__ float4 nnc_lds[];
-  const int b = blockIdx.y;
-  const float4 *rec = LDS_REC ? (const float4 *)nnc_lds : cell_rec + (size_t)b * m;
-  int *cs = (int *)(nnc_lds + (LDS_REC ? m : 0));
-  if (LDS_REC)
-    for (int i = threadIdx.x; i < m; i += 256) nnc_lds[i] = cell_rec[(size_t)b * m + i];
-  for (int i = threadIdx.x; i <= NNC_CELLS; i += 256) cs[i] = cell_start[(size_t)b * (NNC_CELLS + 1) + i];
-  __syncthreads();
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const float *p = points + (size_t)b * 3 * n;
-  const float ux = p[j], uy = p[j + n], uz = p[j + 2 * n];
-  const float h = box[(size_t)b * 4 + 3], inv = 1.0f / h;
-  const int cx = min(max((int)floorf((ux - box[(size_t)b * 4]) * inv), 0), NNC_G - 1);
-  const int cy = min(max((int)floorf((uy - box[(size_t)b * 4 + 1]) * inv), 0), NNC_G - 1);
-  const int cz = min(max((int)floorf((uz - box[(size_t)b * 4 + 2]) * inv), 0), NNC_G - 1);
-  float best0 = INFINITY, best1 = INFINITY, best2 = INFINITY;
-  int i0 = 0, i1 = 0, i2 = 0;
-  // (distance, index) lexicographic: what ascending-index brute force with strict '<' selects
-  auto before = [](float d, int k, float bd, int bi) { return d < bd || (d == bd && k < bi); };
-  // (always_inline: as an out-of-line call the by-reference captures -- the three bests -- would live in scratch)
-  auto consider = [&](const float4 r) __attribute__((always_inline)) {
-    const int k = __float_as_int(r.w);
-    const float d = sqdist3(ux - r.x, uy - r.y, uz - r.z);
-    if (d <= best2) {  // (one compare rejects almost every candidate)
-      // sorted insertion as selects: written with nested ifs + shifts the compiler turned the three bests into a
-      // dynamically indexed scratch array (8x slower)
-      const bool c2 = before(d, k, best2, i2), c1 = before(d, k, best1, i1), c0 = before(d, k, best0, i0);
-      const float n2 = c1 ? best1 : (c2 ? d : best2), n1 = c0 ? best0 : (c1 ? d : best1), n0 = c0 ? d : best0;
-      const int m2 = c1 ? i1 : (c2 ? k : i2), m1 = c0 ? i0 : (c1 ? k : i1), m0 = c0 ? k : i0;
-      best2 = n2;
-      best1 = n1;
-      best0 = n0;
-      i2 = m2;
-      i1 = m1;
-      i0 = m0;
-    }
-  };
-  auto visit_run = [&](int q0, int q1) __attribute__((always_inline)) {  // consecutive cells = consecutive records
-    for (int q = q0; q < q1; q += 4) {  // four independent LDS reads in flight, candidates taken in order
-      float4 r[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) r[u] = rec[min(q + u, q1 - 1)];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (q + u < q1) consider(r[u]);
-    }
-  };
-  for (int rho = 1; rho < NNC_G; ++rho) {
-    const int z0 = max(cz - rho, 0), z1 = min(cz + rho, NNC_G - 1);
-    const int y0 = max(cy - rho, 0), y1 = min(cy + rho, NNC_G - 1);
-    const int x0 = max(cx - rho, 0), x1 = min(cx + rho, NNC_G - 1);
-    for (int z = z0; z <= z1; ++z)
-      for (int y = y0; y <= y1; ++y) {
-        const int row = (z * NNC_G + y) * NNC_G;  // the cells of one x-row are consecutive
-        // rho = 1: the whole 3x3x3 block (ring 0 alone can never end the search); later: the shell of Chebyshev
-        // radius rho -- full rows on its z / y faces, the two end cells on the interior rows
-        const bool face = rho == 1 || z == cz - rho || z == cz + rho || y == cy - rho || y == cy + rho;
-        if (face) {
-          visit_run(cs[row + x0], cs[row + x1 + 1]);
-        } else {
-          if (cx - rho >= 0) visit_run(cs[row + cx - rho], cs[row + cx - rho + 1]);
-          if (cx + rho <= NNC_G - 1) visit_run(cs[row + cx + rho], cs[row + cx + rho + 1]);
-        }
-      }
-    // everything not visited yet is farther than rho * h (in at least one axis the cell index differs by > rho)
-    const float bound = (float)rho * h;
-    if (best2 <= bound * bound * 0.9999f && best2 < INFINITY) break;  // (margin: cell assignment rounds)
-    if (x0 == 0 && y0 == 0 && z0 == 0 && x1 == NNC_G - 1 && y1 == NNC_G - 1 && z1 == NNC_G - 1) break;  // all cells seen
-  }
-  best0 = fmaxf(fminf(1e10f, best0), 1e-10f);
-  best1 = fmaxf(fminf(1e10f, best1), 1e-10f);
-  best2 = fmaxf(fminf(1e10f, best2), 1e-10f);
-  const float d0d1 = best0 * best1, d0d2 = best0 * best2, d1d2 = best1 * best2;
-  const float invw = __fdiv_rn(1.0f, d0d1 + d0d2 + d1d2);
-  float *w = weights + (size_t)b * 3 * n;
-  int *id = indices + (size_t)b * 3 * n;
-  w[j] = d1d2 * invw;
-  id[j] = i0;
-  w[j + n] = d0d2 * invw;
-  id[j + n] = i1;
-  w[j + 2 * n] = d0d1 * invw;
-  id[j + 2 * n] = i2;
-}
-
-#define NNC_MAX_M 8192  // records + cell table in LDS: 16 m + 16.4 KB <= 148 KB
-
-extern "C" size_t p2pb_three_nn_cells_ws_bytes(int b, int m) {
-  return (size_t)b * m * 16 + ((size_t)b * (NNC_CELLS + 1) + (size_t)b * m) * sizeof(int) + (size_t)b * 4 * sizeof(float);
-}
-
-// p2pb_three_nn through a uniform grid over the centres: same idx / w. m >= 3 (records in LDS up to 8192 centres, in L2 above);
-// ws: p2pb_three_nn_cells_ws_bytes(b, m) bytes, 16-byte aligned
-extern "C" int p2pb_three_nn_cells(int b, int m, int n, const float *points, const float *centers, int *idx, float *w,
-                                   void *ws, void *stream) {
-  if (b <= 0 || n <= 0 || m < 3 || m > (1 << 24) || !ws || ((uintptr_t)ws & 15)) return P2PB_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  float4 *cell_rec = (float4 *)ws;
-  int *cell_start = (int *)(cell_rec + (size_t)b * m);
-  int *cell_ids = cell_start + (size_t)b * (NNC_CELLS + 1);
-  float *box = (float *)(cell_ids + (size_t)b * m);
-  const bool in_lds = m <= NNC_MAX_M;
-  const size_t lds = (in_lds ? (size_t)m * 16 : 0) + (NNC_CELLS + 1) * sizeof(int) + 16;
-  static bool once = false;
-  if (!once) {
-    (void)hipFuncSetAttribute((const void *)three_nn_cells_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    once = true;
-  }
-  hipLaunchKernelGGL(nn_cells_build_kernel, dim3(b), dim3(1024), 0, s, m, centers, cell_start, cell_ids, cell_rec, box);
-  if (in_lds)
-    hipLaunchKernelGGL(three_nn_cells_kernel<true>, dim3(cdiv(n, 256), b), dim3(256), lds, s, n, m, points, cell_start, cell_rec,
-                       box, w, idx);
-  else
-    hipLaunchKernelGGL(three_nn_cells_kernel<false>, dim3(cdiv(n, 256), b), dim3(256), lds, s, n, m, points, cell_start, cell_rec,
-                       box, w, idx);
-  return p2pb_launch_status();
-}
-
-template <int CC>
-__global__ __launch_bounds__(256) void three_interp_kernel(int c, int m, int n, const float *__restrict__ cfeat,
-                                                           const int *__restrict__ indices,
-                                                           const float *__restrict__ weights,
-                                                           float *__restrict__ out) {
-  const int b = blockIdx.z;
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int *id = indices + (size_t)b * 3 * n;
-  const float *w = weights + (size_t)b * 3 * n;
-  const int a0 = id[j], a1 = id[j + n], a2 = id[j + 2 * n];
-  const float w0 = w[j], w1 = w[j + n], w2 = w[j + 2 * n];
-  const int c0 = blockIdx.y * CC, c1 = min(c0 + CC, c);
-  for (int l = c0; l < c1; ++l) {
-    const float *f = cfeat + ((size_t)b * c + l) * m;
-    out[((size_t)b * c + l) * n + j] = __fmaf_rn(f[a2], w2, __fmaf_rn(f[a1], w1, f[a0] * w0));
-  }
-}
-
-extern "C" int p2pb_three_nn_interpolate_forward(int b, int c, int m, int n, const float *points,
-                                                 const float *centers, const float *cfeat, int *idx, float *w,
-                                                 float *out, void *stream) {
-  if (b <= 0 || c <= 0 || n <= 0 || m <= 0) return P2PB_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(three_nn_kernel, dim3(cdiv(n, 256), b), dim3(256), 0, s, n, m, points, centers, w, idx);
-  constexpr int CC = 16;
-  hipLaunchKernelGGL(three_interp_kernel<CC>, dim3(cdiv(n, 256), cdiv(c, CC), b), dim3(256), 0, s, c, m, n, cfeat,
-                     idx, w, out);
-  return p2pb_launch_status();
-}
-
-// the two halves of the op as separate entry points: the search depends on coordinates only, so the
-// sampler runs it on a side stream (geometry pipeline) while the feature path is still busy
-extern "C" int p2pb_three_nn(int b, int m, int n, const float *points, const float *centers, int *idx, float *w,
-                             void *stream) {
-  if (b <= 0 || n <= 0 || m <= 0) return P2PB_EINVAL;
-  hipLaunchKernelGGL(three_nn_kernel, dim3(cdiv(n, 256), b), dim3(256), 0, (hipStream_t)stream, n, m, points, centers,
-                     w, idx);
-  return p2pb_launch_status();
-}
-
-extern "C" int p2pb_three_interpolate(int b, int c, int m, int n, const float *cfeat, const int *idx, const float *w,
-                                      float *out, void *stream) {
-  if (b <= 0 || c <= 0 || n <= 0 || m <= 0) return P2PB_EINVAL;
-  constexpr int CC = 16;
-  hipLaunchKernelGGL(three_interp_kernel<CC>, dim3(cdiv(n, 256), cdiv(c, CC), b), dim3(256), 0, (hipStream_t)stream, c,
-                     m, n, cfeat, idx, w, out);
   return p2pb_launch_status();
 }
 

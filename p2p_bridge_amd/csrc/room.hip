@@ -5,7 +5,7 @@
 //     update_prediction_noisy_batches (denoise_room.py:263-289).
 // A room has 10^5..10^6 points and a few hundred patch centres: brute force is ~10^9 distance evaluations (about a
 // millisecond); one WAVE per centre walks the cloud 64 points per step and compacts the hits in index order with
-// ballot + mbcnt, the same idiom as the ball query of neighbors.hip -- two passes (count, fill) because the lists
+// ballot + mbcnt, the same idiom as the ball query of ball_query.hip -- two passes (count, fill) because the lists
 // are ragged.
 #include "common.h"
 

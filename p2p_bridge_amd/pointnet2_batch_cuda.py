@@ -301,7 +301,7 @@ def group_concat(points_coords, centers_coords, points_features, indices):
     return out
 
 
-# ---- the classic PointNet++ operators (PN2/pointnet2_api.cpp:17-29; csrc/pointnet2_legacy.hip) ----------------------
+# ---- the classic PointNet++ operators (PN2/pointnet2_api.cpp:17-29; csrc/ball_query.hip, three_nn.hip) --------------
 # Clouds are POINT-major f32[B,N,3]. The caller allocates every output and passes the sizes as integers, exactly as the
 # reference's layers do (third_party/openpoints/models/layers/{group,subsample,upsampling}.py); the kernels run on the
 # current stream and write into the caller's tensors. The reference's `int` functions return 1, its `void` ones None.

@@ -295,7 +295,7 @@ def test_auction(met, persist_from, monkeypatch):
 @pytest.mark.parametrize("B,N,M,kind", [(3, 8192, 2048, "patch"), (2, 2048, 512, "patch"), (2, 1000, 300, "plane"),
                                          (2, 777, 256, "dups"), (1, 5000, 1024, "outside"), (2, 600, 257, "line")])
 def test_three_nn_grid_search_matches_brute_force(ext, B, N, M, kind, monkeypatch):
-    """the uniform-grid 3-NN (csrc/neighbors.hip three_nn_cells) is exact: same indices (ties by ascending index) and
+    """the uniform-grid 3-NN (csrc/three_nn.hip three_nn_cells) is exact: same indices (ties by ascending index) and
     weights as the brute-force kernel, which is bit-exact against the oracle above"""
     g = torch.Generator().manual_seed(N + M)
     if kind == "patch":

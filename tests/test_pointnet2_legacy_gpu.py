@@ -1,5 +1,5 @@
-"""The nine classic PointNet++ operators of `pointnet2_batch_cuda` (csrc/pointnet2_legacy.hip and the grouping / gather entry
-points they share with the PVCNN operators) against brute-force references written here in numpy.
+"""The nine classic PointNet++ operators of `pointnet2_batch_cuda` (csrc/ball_query.hip, csrc/three_nn.hip, csrc/fps_ref.hip and the grouping / gather
+entry points they share with the PVCNN operators) against brute-force references written here in numpy.
 
 EXACT family: coordinates k/8 with integer k in [-8, 8], so every difference, square and three-term sum is exact in fp32 and
 a squared distance is (sum of integer squares) / 64. The references work on the integers and apply the tie rules of
@@ -62,6 +62,11 @@ def same_bits(got, want, what):
     assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
     bad = got.view(np.int32) != want.view(np.int32)
     assert not bad.any(), f"{what}: {int(bad.sum())} of {bad.size} differ, first at {tuple(np.argwhere(bad)[0])}"
+
+
+def cm(t):
+    """[B, N, K] -> channel-major [B, K, N], contiguous: the layout of the PVCNN operators"""
+    return t.transpose(1, 2).contiguous()
 
 
 # ---- the exact family ---------------------------------------------------------------------------------------------------
@@ -224,6 +229,35 @@ def test_ball_query_exact_cloud_beyond_lds(ext):
         same_bits(idx[b], ball_query_ref(d2_int(ctr[b], pts[b]), 4, nsample, -7), f"ball query idx, cloud {b}")
 
 
+# One scan serves both layouts (csrc/ball_query.hip): global memory (B * m < 2048), the cloud in LDS, a cloud beyond the LDS bound
+BALL_QUERY_ARMS = {
+    "global": lambda: main_case(),
+    "lds": lambda: (main_case()[0], lattice(1100, seed=3)),
+    "beyond_lds": lambda: (lattice(13000, seed=1), lattice(64, seed=3)),  # 3 * 13000 * 4 B = 156 000 > 147 456
+}
+
+
+@pytest.mark.parametrize("radius", [0.25, 0.5])
+@pytest.mark.parametrize("arm", list(BALL_QUERY_ARMS))
+def test_ball_query_layouts_agree(ext, arm, radius):
+    """the channel-major operator on the transposed clouds and the point-major one give the same bits on every row with a
+    hit; without one the first writes zeros and the second leaves the caller's row (-7 here)"""
+    pts, ctr = BALL_QUERY_ARMS[arm]()
+    n, m, nsample = pts.shape[1], ctr.shape[1], 16
+    xyz, new_xyz = dev(cloud(pts)), dev(cloud(ctr))
+    pv = ext.ball_query(cm(new_xyz), cm(xyz), radius, nsample).cpu().numpy()
+    idx = torch.full((B, m, nsample), -7, dtype=I32, device="cuda")
+    assert ext.ball_query_wrapper(B, n, m, radius, nsample, new_xyz, xyz, idx) == 1
+    pn = idx.cpu().numpy()
+    thr = int(round(64 * radius * radius))
+    hit = np.stack([(d2_int(ctr[b], pts[b]) < thr).any(1) for b in range(B)])
+    same_bits(torch.from_numpy(pv[hit]), pn[hit], f"ball query, {arm}, r = {radius}: rows with a hit")
+    assert (pv[~hit] == 0).all() and (pn[~hit] == -7).all()
+    # the small clouds leave centres alone at the small radius (13000 points cover the neighbourhood of every lattice site)
+    if radius == 0.25 and arm != "beyond_lds":
+        assert (~hit).sum() > 0
+
+
 # m = 1, 2: unfilled slots; 257: the main case; 2500: more than one LDS tile of known points
 @pytest.mark.parametrize("m", [1, 2, 3, 257, 2500])
 def test_three_nn_exact(ext, m):
@@ -245,6 +279,35 @@ def test_three_nn_exact(ext, m):
         assert bool(torch.isinf(dist2[:, :, m:]).all()) and bool((idx[:, :, m:] == 0).all())
     if m >= 4:
         assert ties > 0  # equal distances among the nearest four: the tie rule decides
+
+
+def nn3_weights_ref(dist2):
+    """nn3_store_weights (csrc/three_nn.hip) in numpy float32, one IEEE operation each: dist2 f32[B,N,3] -> w f32[B,3,N]"""
+    d = np.maximum(np.minimum(np.float32(1e10), dist2), np.float32(1e-10))
+    assert d.dtype == np.float32
+    d0, d1, d2 = d[..., 0], d[..., 1], d[..., 2]
+    d0d1, d0d2, d1d2 = d0 * d1, d0 * d2, d1 * d2
+    inv = np.float32(1.0) / (d0d1 + d0d2 + d1d2)
+    return np.stack([d1d2 * inv, d0d2 * inv, d0d1 * inv], axis=1)
+
+
+@pytest.mark.parametrize("m", [1, 2, 3, 257, 2500])
+def test_three_nn_layouts_agree(ext, m, monkeypatch):
+    """the channel-major search (brute force, and the grid search where it is the default) finds the indices of the
+    point-major one, and its weights are the weight arithmetic applied to the point-major squared distances, to the bit:
+    duplicates (d = 0 -> 1e-10, products 1e-20) and unfilled slots (+inf -> 1e10, products 1e20) stay in the normal range"""
+    unknown = main_case()[0]
+    known = lattice(m, seed=2) if m > M else main_case()[1][:, :m]
+    xyz, kn = dev(cloud(unknown)), dev(cloud(known))
+    dist2 = torch.empty(B, N, 3, dtype=F32, device="cuda")
+    idx = torch.empty(B, N, 3, dtype=I32, device="cuda")
+    assert ext.three_nn_wrapper(B, N, m, xyz, kn, dist2, idx) is None
+    want_idx, want_w = cm(idx).cpu().numpy(), nn3_weights_ref(dist2.cpu().numpy())
+    for cells in ("0", "1") if m >= 256 else ("0",):  # "0": brute force for every m; "1" (the default): the grid from 256 on
+        monkeypatch.setenv("P2PB_EXPERIMENT", f"nn_cells={cells}")
+        got_idx, got_w = ext.three_nn(cm(xyz), cm(kn))
+        same_bits(got_idx, want_idx, f"three_nn idx, m = {m}, nn_cells = {cells}")
+        same_bits(got_w, want_w, f"three_nn weights, m = {m}, nn_cells = {cells}")
 
 
 def int_features(rng, *shape):
@@ -322,6 +385,14 @@ def test_three_interpolate_exact(ext, c):
     grad = dev(pre)
     assert ext.three_interpolate_grad_wrapper(B, c, N, M, dev(gout), dev(idx), dev(w), grad) is None
     same_bits(grad, interp_grad_ref(gout, idx, w, pre).astype(np.float32), "three_interpolate_grad (adds into its target)")
+
+
+@pytest.mark.parametrize("c", [1, 17])  # 17 crosses the 16-channel chunk of a thread
+def test_three_interpolate_layouts_agree(ext, c):
+    feat, idx, w, _, _ = interp_case(c)
+    out = torch.empty(B, c, N, dtype=F32, device="cuda")
+    assert ext.three_interpolate_wrapper(B, c, M, N, dev(feat), dev(idx), dev(w), out) is None
+    same_bits(ext.three_interpolate(dev(feat), cm(dev(idx)), cm(dev(w))), out.cpu().numpy(), "three_interpolate, both layouts")
 
 
 # ---- the float family ---------------------------------------------------------------------------------------------------

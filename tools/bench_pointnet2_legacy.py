@@ -1,4 +1,4 @@
-"""Times the five classic PointNet++ operators (csrc/pointnet2_legacy.hip; FPS: csrc/fps_ref.hip) at a set-abstraction
+"""Times the five classic PointNet++ operators (csrc/ball_query.hip, csrc/three_nn.hip; FPS: csrc/fps_ref.hip) at a set-abstraction
 shape (B = 16, N = 8192 -> M = 2048, nsample = 32, C = 64) through the `*_wrapper` functions of p2p_bridge_amd/pointnet2_batch_cuda.py, each next to a comparator
 in the same run: what a user of the package could do before these operators existed -- transpose the point-major tensors to
 channel-major, call the existing PVCNN operator, transpose the result back. The comparator is a yardstick for TIME only: its
