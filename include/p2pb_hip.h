@@ -970,6 +970,42 @@ int p2pb_p2m_point_face_subset(int nq, const int *qidx, int np, int nt, const fl
 int p2pb_p2m_face_point_subset(int nq, const int *qidx, int np, int nt, const float *points, const float *tris,
                                float min_triangle_area, float *dist, int *idx, void *stream);
 
+/* point-to-mesh, packed batches with gradients ---------------------------------------------------------------------
+ * The eight pytorch3d._C operators of the reference's metrics/p2m.py ({point_face, face_point, point_edge, edge_point}_dist_
+ * {forward, backward}) as two entry points with a `kind` (csrc/p2m_packed.hip; Python side: p2p_bridge_amd/p2m.py). Pure
+ * additions like the p2pb_p2m_grid_* entry points: P2PB_ABI_VERSION stays 13.
+ * A QUERY is a point (kinds POINT_*) or a primitive (kinds FACE_POINT, EDGE_POINT), a TARGET the other side. points f32[np,3];
+ * prims f32[ns,3,3] (FACE kinds, triangles) or f32[ns,2,3] (EDGE kinds, segments). Example b of the n packed ones owns points
+ * [points_first_idx[b], points_first_idx[b+1]) and primitives [prims_first_idx[b], prims_first_idx[b+1]), the last example
+ * up to np / ns (first indices i64[n], ascending, inside [0, np] / [0, ns]: values outside are clamped, never followed).
+ *
+ * p2pb_p2m_packed_forward: dist f32[nq], idx i64[nq] (nq = np or ns by kind): the squared distance of every query to the
+ *   nearest target OF ITS EXAMPLE and that target's PACKED index, the first minimum in ascending packed index. The pair
+ *   functions are those of p2pb_point_face_dist (csrc/p2m_geom.h), bit for bit: point_triangle_d2 with min_triangle_area for
+ *   the FACE kinds, point_segment_d2 for the EDGE kinds (min_triangle_area unused). The grid is (ceil(max_queries / 256), n):
+ *   a query beyond the first max_queries of its example is NOT written (pytorch3d's contract: pass the largest example's
+ *   count); an example without targets gets dist 3.4e38 and idx -1. n <= 65535.
+ * p2pb_p2m_packed_backward: idx i64[nq] as the forward wrote it, grad_dist f32[nq] -> grad_points f32[np,3], grad_prims shaped
+ *   like prims: the derivative of dist[q] for the branch the forward took (csrc/p2m_grad.h; selections -- inside, the first
+ *   nearest side, the clamp of t, the short-segment test -- are constants) times grad_dist[q]. A query's own row is WRITTEN; an
+ *   idx outside the targets writes a zero row and contributes nothing. Target rows are sums over the queries that chose them:
+ *     default mode: ADDED with fp32 atomics -- the caller passes the target tensor zeroed; order, start = NULL;
+ *     deterministic mode (p2pb_set_deterministic): order i64[nq] = the queries sorted by idx (stable), start i64[nt+1] = the
+ *     first position of every target in it (start[nt] = the end); one wave per target sums its list in ascending position,
+ *     lanes strided, then across lanes in a fixed tree, and WRITES the row (zeros for a target nobody chose): no atomics, no
+ *     zero fill needed, the same bits every run. order / start NULL in that mode: P2PB_EINVAL.
+ * -> 0, P2PB_EINVAL for a bad kind, non-positive np, ns, n or max_queries, n > 65535 or NULL operands. */
+#define P2PB_P2M_POINT_FACE 0
+#define P2PB_P2M_FACE_POINT 1
+#define P2PB_P2M_POINT_EDGE 2
+#define P2PB_P2M_EDGE_POINT 3
+int p2pb_p2m_packed_forward(int kind, int n, int np, int ns, int max_queries, const float *points,
+                            const long long *points_first_idx, const float *prims, const long long *prims_first_idx,
+                            float min_triangle_area, float *dist, long long *idx, void *stream);
+int p2pb_p2m_packed_backward(int kind, int np, int ns, const float *points, const float *prims, const long long *idx,
+                             const float *grad_dist, float min_triangle_area, const long long *order, const long long *start,
+                             float *grad_points, float *grad_prims, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

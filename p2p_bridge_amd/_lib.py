@@ -49,6 +49,8 @@ SYMBOLS = [
     # point-to-mesh grid
     "p2pb_p2m_grid_classify", "p2pb_p2m_grid_count", "p2pb_p2m_grid_fill", "p2pb_p2m_grid_point_face",
     "p2pb_p2m_grid_face_point", "p2pb_p2m_point_face_subset", "p2pb_p2m_face_point_subset",
+    # point-to-mesh, packed batches with gradients
+    "p2pb_p2m_packed_forward", "p2pb_p2m_packed_backward",
 ]
 
 ABI_VERSION = 13  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
