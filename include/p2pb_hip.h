@@ -824,6 +824,15 @@ int p2pb_occupancy_counts(int clouds, int npts, int resolution, int clip_sphere,
  *   and stores the per-channel median (mean of the two middle values in fp32 for an even number, one rounding to fp16; zeros
  *   if no row is left; NaN if a value is NaN), sets done_round[i] = round and decrements remaining. The caller launches
  *   rounds 1, 2, ... until remaining is 0; the lowest unfinished point is always ready.
+ * p2pb_imgfeat_sample_grid: the value that bilinear upsampling (align_corners = false) of a coarse channel-last grid
+ *   f16[b,h,w,c] to (out_h, out_w) has at pixel (clamp(xy.x, 0, out_w-1), clamp(xy.y, 0, out_h-1)), for every point (valid or
+ *   not) of xy i32[b,n,2] -> out f16[b,n,c]: the full-resolution map is never built. Per axis, in fp32:
+ *     src = max((dst + 0.5) * ((float)in / (float)out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1), l1 = src - i0,
+ *     l0 = 1 - l1;   value = ly0 * (lx0*a + lx1*b) + ly1 * (lx0*c + lx1*d)
+ *   with a, b the grid values at row y0, columns x0, x1 and c, d those at row y1, every written operator one fp32 operation
+ *   (no contraction), the value rounded to fp16 once.
+ * p2pb_imgfeat_fuse_grid: p2pb_imgfeat_fuse whose `new` row of (frame f, point i) is p2pb_imgfeat_sample_grid's row, formed in
+ *   registers; one launch for the batch, mean / count updated in place under the same three roundings per frame.
  * -> 0, P2PB_EINVAL for bad sizes or NULL operands. */
 size_t p2pb_imgfeat_visibility_ws_bytes(int b, int n, int width, int height);
 int p2pb_imgfeat_visibility(int b, int n, const double *points, const double *rotation, const double *translation,
@@ -833,6 +842,49 @@ int p2pb_imgfeat_fuse(int b, int n, int c, int hmap, int wmap, const void *maps,
                       void *mean, int *count, void *stream);
 int p2pb_imgfeat_fill_round(int m, int n, int c, int k, const int *missing, const int *nbr, const int *count, void *feat,
                             int *done_round, int round, int *remaining, void *stream);
+int p2pb_imgfeat_sample_grid(int b, int n, int c, int h, int w, int out_h, int out_w, const void *grid, const int *xy, void *out,
+                             void *stream);
+int p2pb_imgfeat_fuse_grid(int b, int n, int c, int h, int w, int out_h, int out_w, const void *grid,
+                           const unsigned char *valid, const int *xy, void *mean, int *count, void *stream);
+
+/* vision transformer ----------------------------------------------------------------------------------------------
+ * The forward of a DINOv2 ViT (the model behind get_dino_features, data/processing/image_features.py:88-111, which the
+ * reference fetches with torch.hub). Python side: p2p_bridge_amd/dinov2.py; kernels: csrc/vit.hip. Pure additions (no ABI
+ * bump, like the p2pb_scan_* entry points).
+ * Layout: tokens are ROW-major, x f32[rows = B*T, C] -- a deliberate exception to the channel-major convention above: every
+ * reduction of a ViT runs over C, the checkpoints' weights are [out, in], the result is read as [B, T, C], and T = 1 + h*w
+ * (235 at 192 x 256) needs no padding this way. Arithmetic: fp32 operands, fp32 FMAs, fp32 results at any magnitude (not the
+ * split-operand arithmetic: p2pb_set_split_terms does not reach these); sums over K and over keys are two-level (tiles of 16 /
+ * 32 terms, then the tile totals). No atomics: the same inputs give the same bits. Pointers 16-byte aligned.
+ * One forward is 3 + 7 * depth launches (87 for ViT-S/14): patch_embed is 2, then per block layernorm, linear (qkv),
+ * attention, linear (proj, RESIDUAL), layernorm, linear (fc1, GELU), linear (fc2, RESIDUAL), then the final layernorm.
+ *
+ * p2pb_vit_layernorm: y[r,:] = (x[r,:] - mean) / sqrt(var + eps) * gamma + beta per row of x f32[rows,c], mean and the BIASED
+ *   variance of x - mean in two passes (never E[x^2] - E[x]^2). y may not alias x.
+ * p2pb_vit_linear: y f32[m,n] from x f32[m,k], w f32[n,k] (a Linear's weight as stored), bias f32[n]; n % 4 == k % 4 == 0.
+ *     P2PB_VIT_EPI_BIAS      y  = x w^T + bias
+ *     P2PB_VIT_EPI_GELU      y  = gelu(x w^T + bias), the exact form 0.5 v (1 + erf(v / sqrt 2))
+ *     P2PB_VIT_EPI_RESIDUAL  y += gamma * (x w^T + bias), gamma f32[n] (LayerScale), y read and written in place
+ * p2pb_vit_patch_embed: images f32[b,3,hp*patch,wp*patch] (already normalised), weight f32[c, 3*patch*patch] (the Conv2d
+ *   weight [c,3,patch,patch] as stored), cls f32[c], pos f32[1 + hp*wp, c] (already interpolated to this grid) ->
+ *   x f32[b, 1 + hp*wp, c]: x[:,0] = cls + pos[0], x[:,1 + p] = patch p (row-major over (hp, wp)) projected + bias + pos[1 + p].
+ *   ws: p2pb_vit_patch_embed_ws_floats(b, hp, wp, patch) floats. patch even, c % 4 == 0, hp*wp <= 65535.
+ * p2pb_vit_attention_forward: qkv f32[b, n, 3*heads*64], channel order (q | k | v) x heads x 64 -> out f32[b, n, heads*64],
+ *   out[i] = sum_j softmax_j((q_i * 64^-0.5) . k_j) v_j over the keys j < n_valid, no mask, no dropout. Keys and values are
+ *   streamed in tiles of 32 with a running max and sum; nothing of size n^2 exists. Rows n_valid .. n-1 are padding: they are
+ *   never read (whatever they hold, NaN included, carries exactly zero weight) and their OUTPUT rows are written as zeros.
+ *   1 <= n_valid <= n. (p2pb_softmax_attention_forward stays the 32-wide channel-major operator of the point networks.)
+ * -> 0, P2PB_EINVAL for bad sizes, a bad epilogue, misaligned or NULL operands. */
+#define P2PB_VIT_EPI_BIAS 0
+#define P2PB_VIT_EPI_GELU 1
+#define P2PB_VIT_EPI_RESIDUAL 2
+int p2pb_vit_layernorm(int rows, int c, const float *x, const float *gamma, const float *beta, float eps, float *y, void *stream);
+int p2pb_vit_linear(int m, int n, int k, const float *x, const float *w, const float *bias, int epilogue, const float *gamma,
+                    float *y, void *stream);
+size_t p2pb_vit_patch_embed_ws_floats(int b, int hp, int wp, int patch);
+int p2pb_vit_patch_embed(int b, int hp, int wp, int patch, int c, const float *images, const float *weight, const float *bias,
+                         const float *cls, const float *pos, float *ws, float *x, void *stream);
+int p2pb_vit_attention_forward(int b, int heads, int n, int n_valid, const float *qkv, float *out, void *stream);
 
 /* scan fusion ---------------------------------------------------------------------------------------------------
  * Depth frames -> one cleaned room cloud: the GPU stages of data/scannetpp/iphone/process_dataset.py:102-283 and arkit_pcl.py

@@ -51,6 +51,9 @@ SYMBOLS = [
     "p2pb_p2m_grid_face_point", "p2pb_p2m_point_face_subset", "p2pb_p2m_face_point_subset",
     # point-to-mesh, packed batches with gradients
     "p2pb_p2m_packed_forward", "p2pb_p2m_packed_backward",
+    # DINOv2 features: the ViT forward, and sampling its token grid at the points
+    "p2pb_vit_layernorm", "p2pb_vit_linear", "p2pb_vit_patch_embed_ws_floats", "p2pb_vit_patch_embed",
+    "p2pb_vit_attention_forward", "p2pb_imgfeat_sample_grid", "p2pb_imgfeat_fuse_grid",
 ]
 
 ABI_VERSION = 13  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
@@ -94,6 +97,7 @@ def lib():
         _lib.p2pb_pairwise_emd_ws_bytes.restype = ctypes.c_size_t
         _lib.p2pb_occupancy_ws_bytes.restype = ctypes.c_size_t
         _lib.p2pb_imgfeat_visibility_ws_bytes.restype = ctypes.c_size_t
+        _lib.p2pb_vit_patch_embed_ws_floats.restype = ctypes.c_size_t
         have = _lib.p2pb_version() if hasattr(_lib, "p2pb_version") else None
         if have != ABI_VERSION:
             bad, _lib = _lib, None

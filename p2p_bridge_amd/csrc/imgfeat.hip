@@ -218,6 +218,113 @@ __global__ __launch_bounds__(256) void fuse_kernel(int b, int n, int c, int hmap
   if (lv == 0 && cnt != cnt0) count[p] = cnt;
 }
 
+// ---- fusion from the coarse grid --------------------------------------------------------------------------------------
+// The DINO branch of the reference upsamples the [h, w] patch grid to the frame's (H, W) with bilinear interpolation
+// (image_features.py:110) and then reads one pixel per visible point. The value of that map at one pixel is a function of four
+// grid rows, so it is formed here, per point, and the map (37.7 MB per 192 x 256 frame of 384 channels) never exists.
+// Contract (include/p2pb_hip.h): per axis src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1),
+// l1 = src - i0, l0 = 1 - l1; value = ly0 * (lx0*a + lx1*b) + ly1 * (lx0*c + lx1*d), each operator one fp32 operation (the file is
+// compiled with -ffp-contract=off), one rounding to fp16.
+struct Lin {
+  int i0, i1;
+  float l0, l1;
+};
+__device__ __forceinline__ Lin lin_axis(int dst, int in, int out) {
+  const float scale = (float)in / (float)out;
+  const float src = fmaxf(((float)dst + 0.5f) * scale - 0.5f, 0.0f);
+  Lin r;
+  r.i0 = min((int)src, in - 1);  // (src >= 0: truncation is floor; src < in - 0.5 for every dst < out, the min guards memory)
+  r.i1 = min(r.i0 + 1, in - 1);
+  r.l1 = src - (float)r.i0;
+  r.l0 = 1.0f - r.l1;
+  return r;
+}
+__device__ __forceinline__ _Float16 bilerp(_Float16 a, _Float16 b, _Float16 c, _Float16 d, const Lin &lx, const Lin &ly) {
+  const float top = lx.l0 * (float)a + lx.l1 * (float)b;
+  const float bot = lx.l0 * (float)c + lx.l1 * (float)d;
+  return (_Float16)(ly.l0 * top + ly.l1 * bot);
+}
+__device__ __forceinline__ f16v8 bilerp_v(const f16v8 &a, const f16v8 &b, const f16v8 &c, const f16v8 &d, const Lin &lx,
+                                          const Lin &ly) {
+  f16v8 r;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) r[e] = bilerp(a[e], b[e], c[e], d[e], lx, ly);
+  return r;
+}
+__device__ __forceinline__ _Float16 bilerp_v(const _Float16 &a, const _Float16 &b, const _Float16 &c, const _Float16 &d,
+                                             const Lin &lx, const Lin &ly) {
+  return bilerp(a, b, c, d, lx, ly);
+}
+// vector v of the sampled row of one frame's grid g f16[h,w,c] at pixel (x, y) of the (out_h, out_w) map, coordinates clamped
+template <int VEC>
+__device__ __forceinline__ typename F16Vec<VEC>::T grid_row(const _Float16 *__restrict__ g, int h, int w, int c, int out_h,
+                                                           int out_w, int x, int y, int v) {
+  typedef typename F16Vec<VEC>::T V;
+  const Lin lx = lin_axis(min(max(x, 0), out_w - 1), w, out_w), ly = lin_axis(min(max(y, 0), out_h - 1), h, out_h);
+  const V *r0 = (const V *)(g + (size_t)ly.i0 * w * c), *r1 = (const V *)(g + (size_t)ly.i1 * w * c);
+  const size_t nvec = (size_t)(c / VEC);
+  return bilerp_v(r0[lx.i0 * nvec + v], r0[lx.i1 * nvec + v], r1[lx.i0 * nvec + v], r1[lx.i1 * nvec + v], lx, ly);
+}
+
+// one thread per (frame, point, vector of channels)
+template <int VEC>
+__global__ __launch_bounds__(256) void sample_grid_kernel(long total, int n, int c, int h, int w, int out_h, int out_w,
+                                                          const _Float16 *__restrict__ grid, const int *__restrict__ xy,
+                                                          _Float16 *__restrict__ out) {
+  typedef typename F16Vec<VEC>::T V;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int nvec = c / VEC;
+  const int v = (int)(e % nvec);
+  const long fp = e / nvec;  // frame * n + point
+  const long f = fp / n;
+  *((V *)(out + (size_t)fp * c) + v) =
+      grid_row<VEC>(grid + (size_t)f * h * w * c, h, w, c, out_h, out_w, xy[(size_t)fp * 2], xy[(size_t)fp * 2 + 1], v);
+}
+
+// fuse_kernel with the gathered map row replaced by the sampled grid row: same decomposition, same three roundings per frame
+template <int VEC>
+__global__ __launch_bounds__(256) void fuse_grid_kernel(int b, int n, int c, int h, int w, int out_h, int out_w, int lanes, int ppb,
+                                                        const _Float16 *__restrict__ grid, const unsigned char *__restrict__ valid,
+                                                        const int *__restrict__ xy, _Float16 *__restrict__ mean,
+                                                        int *__restrict__ count) {
+  typedef typename F16Vec<VEC>::T V;
+  const int lp = (int)threadIdx.x / lanes, lv = (int)threadIdx.x % lanes;
+  const long p = (long)blockIdx.x * ppb + lp;
+  const bool act = lp < ppb && p < n;
+  const int cnt0 = act ? count[p] : 0;
+  __syncthreads();
+  if (!act) return;
+  const int nvec = c / VEC;
+  int cnt = cnt0;
+  for (int v = lv; v < nvec; v += lanes) {
+    V *mp = (V *)(mean + (size_t)p * c) + v;
+    V m = *mp;
+    cnt = cnt0;
+    for (int f0 = 0; f0 < b; f0 += 2) {
+      bool ok[2];
+      V row[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int f = f0 + u;
+        ok[u] = f < b && valid[(size_t)f * n + p] != 0;
+        if (ok[u]) {
+          const size_t o = ((size_t)f * n + p) * 2;
+          row[u] = grid_row<VEC>(grid + (size_t)f * h * w * c, h, w, c, out_h, out_w, xy[o], xy[o + 1], v);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+        if (ok[u]) {
+          ++cnt;
+          mean_step_v(m, row[u], (float)cnt);
+        }
+    }
+    if (cnt != cnt0) *mp = m;
+  }
+  if (lv == 0 && cnt != cnt0) count[p] = cnt;
+}
+
 // ---- fill -------------------------------------------------------------------------------------------------------------
 // The reference fills the unobserved points in ascending index, in place (image_features.py:314-324): point i takes the
 // per-channel median of the rows of its k nearest points that are not all-zero AT THAT MOMENT -- observed points, and unobserved
@@ -349,6 +456,47 @@ extern "C" int p2pb_imgfeat_fuse(int b, int n, int c, int hmap, int wmap, const 
   const bool vec = c % 8 == 0 && (((size_t)maps | (size_t)mean) & 15) == 0;  // 16-byte rows at 16-byte addresses
   return vec ? fuse_launch<8>(b, n, c, hmap, wmap, (const _Float16 *)maps, valid, xy, (_Float16 *)mean, count, s)
              : fuse_launch<1>(b, n, c, hmap, wmap, (const _Float16 *)maps, valid, xy, (_Float16 *)mean, count, s);
+}
+
+static bool grid_args_ok(int b, int n, int c, int h, int w, int out_h, int out_w) {
+  if (b <= 0 || n <= 0 || c <= 0 || h <= 0 || w <= 0 || out_h <= 0 || out_w <= 0) return false;
+  return (size_t)b * n <= (size_t)INT_MAX && (size_t)h * w <= (size_t)INT_MAX / 2;
+}
+
+extern "C" int p2pb_imgfeat_sample_grid(int b, int n, int c, int h, int w, int out_h, int out_w, const void *grid, const int *xy,
+                                        void *out, void *stream) {
+  if (!grid_args_ok(b, n, c, h, w, out_h, out_w) || !grid || !xy || !out) return P2PB_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = c % 8 == 0 && (((size_t)grid | (size_t)out) & 15) == 0;
+  const long total = (long)b * n * (vec ? c / 8 : c);
+  if (total / 256 >= (long)INT_MAX) return P2PB_EINVAL;
+  if (vec)
+    hipLaunchKernelGGL(sample_grid_kernel<8>, dim3(cdiv(total, 256)), dim3(256), 0, s, total, n, c, h, w, out_h, out_w,
+                       (const _Float16 *)grid, xy, (_Float16 *)out);
+  else
+    hipLaunchKernelGGL(sample_grid_kernel<1>, dim3(cdiv(total, 256)), dim3(256), 0, s, total, n, c, h, w, out_h, out_w,
+                       (const _Float16 *)grid, xy, (_Float16 *)out);
+  return p2pb_launch_status();
+}
+
+template <int VEC>
+static int fuse_grid_launch(int b, int n, int c, int h, int w, int out_h, int out_w, const _Float16 *grid,
+                            const unsigned char *valid, const int *xy, _Float16 *mean, int *count, hipStream_t s) {
+  const int nvec = c / VEC;
+  const int lanes = nvec < 256 ? nvec : 256;
+  const int ppb = 256 / lanes;
+  hipLaunchKernelGGL(fuse_grid_kernel<VEC>, dim3(cdiv(n, ppb)), dim3(256), 0, s, b, n, c, h, w, out_h, out_w, lanes, ppb, grid,
+                     valid, xy, mean, count);
+  return p2pb_launch_status();
+}
+
+extern "C" int p2pb_imgfeat_fuse_grid(int b, int n, int c, int h, int w, int out_h, int out_w, const void *grid,
+                                      const unsigned char *valid, const int *xy, void *mean, int *count, void *stream) {
+  if (!grid_args_ok(b, n, c, h, w, out_h, out_w) || !grid || !valid || !xy || !mean || !count) return P2PB_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = c % 8 == 0 && (((size_t)grid | (size_t)mean) & 15) == 0;
+  return vec ? fuse_grid_launch<8>(b, n, c, h, w, out_h, out_w, (const _Float16 *)grid, valid, xy, (_Float16 *)mean, count, s)
+             : fuse_grid_launch<1>(b, n, c, h, w, out_h, out_w, (const _Float16 *)grid, valid, xy, (_Float16 *)mean, count, s);
 }
 
 extern "C" int p2pb_imgfeat_fill_round(int m, int n, int c, int k, const int *missing, const int *nbr, const int *count,

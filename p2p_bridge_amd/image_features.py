@@ -5,6 +5,7 @@ denoise_room / room_data consume (`point_features="dino"`).
     project_point_cloud_batch   :114-143   fp64 projection of the scan into a batch of frames
     visible_points              :146-190   the occlusion test (with the projection in front of it)
     update_features             :223-279   sample the frames' feature maps, fp16 running mean per point
+    sample_grid / update_features_from_grid  the same from the coarse DINO token grid, without the upsampled map (:110)
     interpolate_missing_features :282-326  unobserved points take the median of their filled / observed neighbours
     frame_stride                :411-427   every n-th frame
     fuse_scene                  :399-514   the driver (scene FILE reading stays with the caller), save_features :514
@@ -20,7 +21,7 @@ Deviations from the reference, all deliberate:
     to frame b's points, as the function's docstring and the RGB path describe;
   * the reference's RGB branch calls a numpy function on CUDA tensors (:487-492) and cannot run; here "rgb" fuses the image
     itself as a 3-channel fp16 map;
-  * the DINOv2 model is the caller's (`feature_fn`): torch.hub is a download;
+  * the DINOv2 model is `dinov2.DinoV2` from a checkpoint file, or the caller's (`feature_fn`): torch.hub is a download;
   * COLMAP text, the pose JSON and the PNGs are read by the caller.
 """
 import ctypes
@@ -205,6 +206,100 @@ def update_features(mean, count, maps, valid, xy):
     return out
 
 
+# ---- fusion from the coarse grid -------------------------------------------------------------------------------------
+def _lin_axis(dst, size_in, size_out):
+    """the bilinear coordinates of one axis under the contract of include/p2pb_hip.h (p2pb_imgfeat_sample_grid): every
+    operator one fp32 torch operation -> (i0, i1 int64, l0, l1 fp32)"""
+    scale = torch.tensor(float(size_in), dtype=F32, device=dst.device) / torch.tensor(float(size_out), dtype=F32, device=dst.device)
+    src = (((dst.to(F32) + 0.5) * scale) - 0.5).clamp_min(0.0)
+    i0 = src.to(torch.int64).clamp_max(size_in - 1)  # (src >= 0: truncation is floor)
+    i1 = (i0 + 1).clamp_max(size_in - 1)
+    l1 = src - i0.to(F32)
+    return i0, i1, 1.0 - l1, l1
+
+
+def sample_grid_torch(grid, out_size, xy):
+    """`sample_grid` with torch operators on whichever device holds the tensors (the CPU path and the operator-level yardstick)"""
+    b, h, w, c = grid.shape
+    out_h, out_w = int(out_size[0]), int(out_size[1])
+    x = xy[..., 0].long().clamp(0, out_w - 1)
+    y = xy[..., 1].long().clamp(0, out_h - 1)
+    x0, x1, lx0, lx1 = _lin_axis(x, w, out_w)
+    y0, y1, ly0, ly1 = _lin_axis(y, h, out_h)
+    f = torch.arange(b, device=grid.device)[:, None]
+    lx0, lx1, ly0, ly1 = lx0[..., None], lx1[..., None], ly0[..., None], ly1[..., None]
+    top = lx0 * grid[f, y0, x0].float() + lx1 * grid[f, y0, x1].float()
+    bot = lx0 * grid[f, y1, x0].float() + lx1 * grid[f, y1, x1].float()
+    return (ly0 * top + ly1 * bot).half()
+
+
+def _check_grid(name, grid, out_size, xy):
+    _check(grid, F16, (None, None, None, None), "grid")
+    b, h, w, c = grid.shape
+    _check(xy, I32, (b, None, 2), "xy")
+    n = xy.shape[1]
+    out_h, out_w = int(out_size[0]), int(out_size[1])
+    if min(b, h, w, c, n, out_h, out_w) < 1 or b * n >= 2 ** 31 or h * w >= 2 ** 30:
+        raise ValueError(f"{name}: grid {list(grid.shape)}, out_size {(out_h, out_w)}, N={n} out of range")
+    return b, h, w, c, n, out_h, out_w
+
+
+def sample_grid(grid, out_size, xy):
+    """The value that bilinear upsampling (align_corners=False) of the coarse grid f16[B,h,w,C] to out_size = (H, W) has at the
+    pixels xy i32[B,N,2] (x, y; clamped to the map) -> f16[B,N,C], without building the map. Evaluated in fp32 from the fp16
+    grid, rounded to fp16 once; per axis src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1),
+    l1 = src - i0, l0 = 1 - l1, value = ly0 * (lx0*a + lx1*b) + ly1 * (lx0*c + lx1*d) (contract: include/p2pb_hip.h). Within one
+    fp16 ulp of F.interpolate(grid.float(), mode="bilinear").half() at those pixels."""
+    like = grid
+    grid, xy = _tensor(grid, "grid"), _tensor(xy, "xy")
+    dev = _one_device("sample_grid", grid, xy)
+    b, h, w, c, n, out_h, out_w = _check_grid("sample_grid", grid, out_size, xy)
+    if dev.type != "cuda":
+        return _back(sample_grid_torch(grid, (out_h, out_w), xy), like)
+    out = torch.empty(b, n, c, dtype=F16, device=dev)
+    ci = ctypes.c_int
+    call("p2pb_imgfeat_sample_grid", ci(b), ci(n), ci(c), ci(h), ci(w), ci(out_h), ci(out_w), ptr(grid), ptr(xy), ptr(out),
+         stream_ptr())
+    return out
+
+
+def update_features_from_grid_torch(mean, count, grid, out_size, valid, xy):
+    """`update_features_from_grid` with torch operators: `sample_grid_torch` rows folded in like `update_features_torch`"""
+    for f in range(grid.shape[0]):
+        idx = torch.nonzero(valid[f]).flatten()
+        if idx.numel() == 0:
+            continue
+        new = sample_grid_torch(grid[f:f + 1], out_size, xy[f:f + 1, idx])[0].float()
+        cnt = count[idx] + 1
+        count[idx] = cnt
+        m = mean[idx].float()
+        d = (new - m).half()
+        q = (d.float() / cnt.float()[:, None]).half()
+        mean[idx] = (m + q.float()).half()
+    return mean, count
+
+
+def update_features_from_grid(mean, count, grid, out_size, valid, xy):
+    """`update_features` whose rows are `sample_grid(grid, out_size, xy)`: the running mean of the bilinearly upsampled map's
+    pixels, IN PLACE, without the map. mean f16[N,C], count i32[N], grid f16[B,h,w,C] channel-last (the fp16 patch tokens),
+    out_size = (H, W) of the map that is not built, valid bool[B,N], xy i32[B,N,2]. Frames in order; per valid point count += 1,
+    mean += (new - mean) / count, every operator rounded to fp16 once from an fp32 evaluation. One launch for the whole batch on
+    a GPU. -> (mean, count)"""
+    out = (mean, count)
+    mean, count, grid = _tensor(mean, "mean"), _tensor(count, "count"), _tensor(grid, "grid")
+    valid, xy = _tensor(valid, "valid"), _tensor(xy, "xy")
+    dev = _one_device("update_features_from_grid", mean, count, grid, valid, xy)
+    b, h, w, c, n, out_h, out_w = _check_grid("update_features_from_grid", grid, out_size, xy)
+    _check(mean, F16, (n, c), "mean"), _check(count, I32, (n,), "count"), _check(valid, torch.bool, (b, n), "valid")
+    if dev.type != "cuda":
+        update_features_from_grid_torch(mean, count, grid, (out_h, out_w), valid, xy)
+        return out
+    ci = ctypes.c_int
+    call("p2pb_imgfeat_fuse_grid", ci(b), ci(n), ci(c), ci(h), ci(w), ci(out_h), ci(out_w), ptr(grid), ptr(valid.view(U8)),
+         ptr(xy), ptr(mean), ptr(count), stream_ptr())
+    return out
+
+
 # ---- fill ------------------------------------------------------------------------------------------------------------
 def _neighbours_cpu(points, missing, k):
     """the k nearest points of the cloud per missing point (fp64 distances of the fp32 coordinates, ties by ascending index)"""
@@ -305,18 +400,21 @@ def frame_stride(total, sampling_rate=5, autoskip=False):
 
 @torch.no_grad()
 def fuse_scene(points, frames, feature_type="rgb", feature_fn=None, batch_size=2, mask_size=(192, 256),
-               intrinsic_scale=256 / 1920, sampling_rate=5, autoskip=False, k=10, device=None):
+               intrinsic_scale=256 / 1920, sampling_rate=5, autoskip=False, k=10, device=None, dino_from_grid=False):
     """The per-scene loop of process_scene (:399-514) -> features f16[C,N'] (tensor on `device`), the transposed layout the
     data sets read; N' = the rows of `points` without NaN / inf (:403-405).
     points [N,3]; frames: a sequence of dicts {image f32[H,W,3] in [0,1], intrinsic 3x3 (full-resolution; rows 0-1 are scaled
     by intrinsic_scale, :466), world_to_camera 4x4}; every frame_stride(len(frames))-th is used, in batches of batch_size.
     mask_size = (height, width) of the occlusion mask. feature_type "rgb": the image itself as a 3-channel fp16 map;
-    "dino": feature_fn(images f16[B,3,H,W]) -> f16[B,C,h,w] (the caller's DINOv2 patch tokens), upsampled to (H, W) with
-    F.interpolate(mode="bilinear") as :110 does. device: default the device of `points` (cpu for numpy)."""
+    "dino": feature_fn(images f16[B,3,H,W]) -> f16[B,C,h,w] (DINOv2 patch tokens: `dinov2.feature_fn(model)`, or the caller's
+    own model), upsampled to (H, W) with F.interpolate(mode="bilinear") as :110 does. dino_from_grid=True (opt-in) never builds
+    that [B,H,W,C] map: the token grid is sampled at the points' pixels (`update_features_from_grid`; fp32 evaluation of the
+    fp16 grid, within one fp16 ulp of the map's values, so the features differ from the default path's in the last place).
+    device: default the device of `points` (cpu for numpy)."""
     if feature_type not in ("rgb", "dino"):
         raise ValueError(f"fuse_scene: feature_type {feature_type!r} is neither 'rgb' nor 'dino'")
     if feature_type == "dino" and feature_fn is None:
-        raise ValueError("fuse_scene: feature_type 'dino' needs feature_fn (the caller's DINOv2 model)")
+        raise ValueError("fuse_scene: feature_type 'dino' needs feature_fn (dinov2.feature_fn(model), or the caller's DINOv2 model)")
     points = torch.as_tensor(points)
     dev = torch.device(device) if device is not None else points.device
     points = points.to(dev, F64)
@@ -339,6 +437,13 @@ def fuse_scene(points, frames, feature_type="rgb", feature_fn=None, batch_size=2
         trans = torch.from_numpy(np.ascontiguousarray(w2c[:, :3, 3])).to(dev)
         valid, xy = visible_points(points, rot, trans, torch.from_numpy(cam).to(dev), width, height)
         images = torch.stack([torch.as_tensor(f["image"], dtype=F32) for f in fr]).to(dev)  # [B,H,W,3]
+        if feature_type == "dino" and dino_from_grid:
+            grid = feature_fn(images.permute(0, 3, 1, 2).to(F16).contiguous()).permute(0, 2, 3, 1).to(F16).contiguous()
+            if mean is None:
+                mean = torch.zeros(n, grid.shape[-1], dtype=F16, device=dev)
+                count = torch.zeros(n, dtype=I32, device=dev)
+            update_features_from_grid(mean, count, grid, tuple(images.shape[1:3]), valid, xy)
+            continue
         if feature_type == "rgb":
             maps = images.to(F16).contiguous()
         else:
