@@ -874,6 +874,23 @@ int p2pb_imgfeat_fuse_grid(int b, int n, int c, int h, int w, int out_h, int out
  *   streamed in tiles of 32 with a running max and sum; nothing of size n^2 exists. Rows n_valid .. n-1 are padding: they are
  *   never read (whatever they hold, NaN included, carries exactly zero weight) and their OUTPUT rows are written as zeros.
  *   1 <= n_valid <= n. (p2pb_softmax_attention_forward stays the 32-wide channel-major operator of the point networks.)
+ *
+ * The same forward with fp16 matrix operands (csrc/vit_f16.hip; DinoV2(precision="fp16")): the arithmetic the reference runs
+ * under fp16 autocast. Only the OPERANDS of matrix products are fp16, each rounded once to nearest-even by the IEEE conversion
+ * (beyond +-65504: +-inf, as torch.Tensor.half(); nothing saturates, nothing checks): products run on
+ * v_mfma_f32_32x32x16_f16 with fp32 accumulators, and bias, GELU, LayerScale, the residual stream, softmax and the LayerNorm
+ * statistics stay fp32. Patch embedding and the final norm use the fp32 entry points above. Same launch count, no atomics.
+ * Pure additions (no ABI bump). fp16 buffers are passed as void *.
+ * p2pb_vit_layernorm_f16: p2pb_vit_layernorm with y f16[rows,c]: the fp32 result rounded once (the bits of `.half()` of it).
+ * p2pb_vit_linear_f16: x f16[m,k], w f16[n,k], bias f32[n]; n % 64 == 0 and k % 32 == 0 (every DINOv2 layer: C = 64 * heads),
+ *   any m >= 1 (no padded row is read or written).
+ *     P2PB_VIT_EPI_BIAS      y f16[m,n]  = x w^T + bias
+ *     P2PB_VIT_EPI_GELU      y f16[m,n]  = gelu(x w^T + bias)
+ *     P2PB_VIT_EPI_RESIDUAL  y f32[m,n] += gamma * (x w^T + bias), gamma f32[n], y read and written in place
+ * p2pb_vit_attention_forward_f16: qkv f16[b, n, 3*heads*64] -> out f16[b, n, heads*64], the contract of
+ *   p2pb_vit_attention_forward (keys < n_valid only, padded rows never read, padded output rows zeros). Both products on the
+ *   matrix pipe; the logits, the running max and sum are fp32; the un-normalised weights exp(s - max) enter P.V rounded to
+ *   fp16, the sum that divides the result is the fp32 one.
  * -> 0, P2PB_EINVAL for bad sizes, a bad epilogue, misaligned or NULL operands. */
 #define P2PB_VIT_EPI_BIAS 0
 #define P2PB_VIT_EPI_GELU 1
@@ -885,6 +902,10 @@ size_t p2pb_vit_patch_embed_ws_floats(int b, int hp, int wp, int patch);
 int p2pb_vit_patch_embed(int b, int hp, int wp, int patch, int c, const float *images, const float *weight, const float *bias,
                          const float *cls, const float *pos, float *ws, float *x, void *stream);
 int p2pb_vit_attention_forward(int b, int heads, int n, int n_valid, const float *qkv, float *out, void *stream);
+int p2pb_vit_layernorm_f16(int rows, int c, const float *x, const float *gamma, const float *beta, float eps, void *y, void *stream);
+int p2pb_vit_linear_f16(int m, int n, int k, const void *x, const void *w, const float *bias, int epilogue, const float *gamma,
+                        void *y, void *stream);
+int p2pb_vit_attention_forward_f16(int b, int heads, int n, int n_valid, const void *qkv, void *out, void *stream);
 
 /* scan fusion ---------------------------------------------------------------------------------------------------
  * Depth frames -> one cleaned room cloud: the GPU stages of data/scannetpp/iphone/process_dataset.py:102-283 and arkit_pcl.py

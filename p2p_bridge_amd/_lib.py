@@ -54,6 +54,7 @@ SYMBOLS = [
     # DINOv2 features: the ViT forward, and sampling its token grid at the points
     "p2pb_vit_layernorm", "p2pb_vit_linear", "p2pb_vit_patch_embed_ws_floats", "p2pb_vit_patch_embed",
     "p2pb_vit_attention_forward", "p2pb_imgfeat_sample_grid", "p2pb_imgfeat_fuse_grid",
+    "p2pb_vit_layernorm_f16", "p2pb_vit_linear_f16", "p2pb_vit_attention_forward_f16",
 ]
 
 ABI_VERSION = 13  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)

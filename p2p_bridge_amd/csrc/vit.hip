@@ -19,45 +19,11 @@
 // Launches of one forward_features call: 2 (im2col + class rows, patch GEMM) + 7 per block (norm1, qkv, attention, proj with
 // the LayerScale residual, norm2, fc1 with GELU, fc2 with the LayerScale residual) + 1 (final norm) = 3 + 7 * depth:
 // 87 for ViT-S/14 and ViT-B/14 (depth 12), 171 for ViT-L/14 (depth 24).
-#include "common.h"
+#include "vit_common.h"
 
 #include <limits.h>
 
 namespace {
-
-// ---- LayerNorm --------------------------------------------------------------------------------------------------------
-// one wave per token, two passes over the row (the second hits the cache): mean, then the biased variance of the deviations
-// x - mean (and their own small mean, which corrects the first pass's rounding). Never E[x^2] - E[x]^2 of the values, which
-// cancels for a stream whose mean is far above its spread.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;  // (xor butterfly: every lane holds the same bits)
-}
-
-__global__ __launch_bounds__(256) void vit_layernorm_kernel(int rows, int c, const float *__restrict__ x,
-                                                            const float *__restrict__ gamma, const float *__restrict__ beta,
-                                                            float eps, float *__restrict__ y) {
-  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const int lane = lane_id();
-  const float *xr = x + (size_t)r * c;
-  float s = 0.0f;
-  for (int i = lane; i < c; i += 64) s += xr[i];
-  const float mean0 = wave_sum(s) / (float)c;  // off by the rounding of a sum of c terms of the stream's magnitude
-  float q = 0.0f, e = 0.0f;
-  for (int i = lane; i < c; i += 64) {
-    const float d = xr[i] - mean0;
-    e += d;
-    q = __fmaf_rn(d, d, q);
-  }
-  // the residual mean of the deviations corrects the first estimate: sum (x - mean)^2 = sum d^2 - c * de^2, de << |d|
-  const float de = wave_sum(e) / (float)c;
-  const float mean = mean0 + de;
-  const float rstd = 1.0f / sqrtf(fmaxf(wave_sum(q) / (float)c - de * de, 0.0f) + eps);
-  float *yr = y + (size_t)r * c;
-  for (int i = lane; i < c; i += 64) yr[i] = (xr[i] - mean) * rstd * gamma[i] + beta[i];
-}
 
 // ---- linear layers ----------------------------------------------------------------------------------------------------
 // y[m, n] = epilogue(sum_k x[m, k] * w[n, k] + bias[n]). A 64 x 64 output tile per 256-thread workgroup, 4 x 4 per thread, K in
@@ -69,8 +35,6 @@ __global__ __launch_bounds__(256) void vit_layernorm_kernel(int rows, int c, con
 #define VG_LD (VG_BM + 4)  // LDS row pitch in floats: 16-byte aligned rows
 
 #define VIT_EPI_PATCH 3  // internal: row m = (image, patch) goes to token row image * (P + 1) + 1 + patch, + pos[1 + patch]
-
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 __device__ __forceinline__ float4 vg_load(const float *__restrict__ base, int ld, int row, int nrows, int k, int kdim) {
   if (row < nrows && k < kdim) return *reinterpret_cast<const float4 *>(base + (size_t)row * ld + k);  // (kdim % 4 == 0)
@@ -309,15 +273,13 @@ __global__ __launch_bounds__(256) void vit_attention_kernel(int heads, int n, in
   }
 }
 
-static inline bool aligned16(const void *p) { return ((size_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" int p2pb_vit_layernorm(int rows, int c, const float *x, const float *gamma, const float *beta, float eps, float *y,
                                   void *stream) {
   if (rows <= 0 || c <= 0 || !(eps >= 0.0f)) return P2PB_EINVAL;
   if (!x || !gamma || !beta || !y) return P2PB_EINVAL;
-  hipLaunchKernelGGL(vit_layernorm_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, c, x, gamma, beta, eps,
+  hipLaunchKernelGGL(vit_layernorm_kernel<float>, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, c, x, gamma, beta, eps,
                      y);
   return p2pb_launch_status();
 }

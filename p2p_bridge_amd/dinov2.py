@@ -13,13 +13,22 @@ The reference fetches the model with torch.hub; here it is built from a checkpoi
     get_dino_features         :88-111: normalise, crop to patch multiples, patch tokens .half(), reshape, bilinear upsample
     feature_fn                the callable `image_features.fuse_scene` expects
 
-CUDA tensors run the kernels of csrc/vit.hip (include/p2pb_hip.h, "vision transformer"): 3 + 7 * depth launches per
-`forward_features`, tokens row-major f32[B*T, C]; there is no fallback from them. CPU tensors take a torch path under the same
-definition (F.linear, F.layer_norm, exact-erf GELU, softmax attention with q scaled by 64^-0.5), which is what the CPU tests hold
-against the stored float64 results of `transformers.Dinov2Model`.
+CUDA tensors run the kernels of csrc/vit.hip and csrc/vit_f16.hip (include/p2pb_hip.h, "vision transformer"): 3 + 7 * depth
+launches per `forward_features`, tokens row-major [B*T, C]; there is no fallback from them. CPU tensors take a torch path under
+the same definition (F.linear, F.layer_norm, exact-erf GELU, softmax attention with q scaled by 64^-0.5), which is what the CPU
+tests hold against the stored float64 results of `transformers.Dinov2Model`.
 
-Arithmetic: fp32 operands and results (README "Arithmetic"). The reference runs the model under fp16 autocast (:494) and then
-takes `.half()` of the tokens; here the forward is fp32 and the tokens are rounded to fp16 once, where that `.half()` stands.
+Arithmetic, `precision="fp32"` (the default; README "Arithmetic"): fp32 operands and results. The reference runs the model under
+fp16 autocast (:494) and then takes `.half()` of the tokens; here the forward is fp32 and the tokens are rounded to fp16 once,
+where that `.half()` stands.
+`precision="fp16"` is the reference's arithmetic on the matrix pipe (csrc/vit_f16.hip): ONLY the operands of the matrix products
+are fp16, each rounded once to nearest-even -- the outputs of norm1 and norm2, the qkv rows, the softmax weights entering P.V,
+the attention output, the post-GELU activations and the weights of attn.qkv, attn.proj, mlp.fc1 and mlp.fc2 (made by `.half()`
+once per model and cached; `load_state_dict` and `.to()` / `.cuda()` drop the cache). The residual stream, LayerNorm statistics,
+softmax, bias, GELU, LayerScale and every accumulation stay fp32, patch embedding and the final norm run the fp32 kernels, and
+`forward_features` returns fp32 as before. The conversion is IEEE: a value beyond +-65504 becomes +-inf, as `Tensor.half()` and
+the reference under autocast make it -- nothing saturates and the hot path checks nothing, so a checkpoint whose post-GELU
+activations leave the fp16 range needs `precision="fp32"`. A CPU model in fp16 mode restates the same roundings in torch.
 
 Position embedding: the [1 + grid^2, C] table is interpolated ON THE HOST in fp32 with F.interpolate(mode="bicubic",
 antialias=False), once per (h, w), and cached (plumbing, not hot; the same table feeds both paths). `interpolate_offset == 0`
@@ -60,15 +69,18 @@ def _f32_cuda(t, name):
     return t
 
 
-def layernorm(x, weight, bias, eps=1e-6):
-    """LayerNorm over the last axis of x f32[..., C] (two-pass, biased variance) -> a new tensor"""
+def layernorm(x, weight, bias, eps=1e-6, out_dtype=F32):
+    """LayerNorm over the last axis of x f32[..., C] (two-pass, biased variance) -> a new tensor; out_dtype=torch.float16: the
+    same fp32 result rounded once in the kernel (the bits of `layernorm(...).half()`)"""
     c = x.shape[-1]
     _f32_cuda(x, "x"), _f32_cuda(weight, "weight"), _f32_cuda(bias, "bias")
     if weight.shape != (c,) or bias.shape != (c,) or x.numel() == 0:
         raise ValueError(f"layernorm: x {list(x.shape)}, weight {list(weight.shape)}, bias {list(bias.shape)}")
-    y = torch.empty_like(x)
-    call("p2pb_vit_layernorm", ctypes.c_int(x.numel() // c), ctypes.c_int(c), ptr(x), ptr(weight), ptr(bias),
-         ctypes.c_float(eps), ptr(y), stream_ptr())
+    if out_dtype not in (F32, F16):
+        raise ValueError(f"layernorm: out_dtype {out_dtype} is not float32 or float16")
+    y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    call("p2pb_vit_layernorm" if out_dtype == F32 else "p2pb_vit_layernorm_f16", ctypes.c_int(x.numel() // c), ctypes.c_int(c),
+         ptr(x), ptr(weight), ptr(bias), ctypes.c_float(eps), ptr(y), stream_ptr())
     return y
 
 
@@ -106,6 +118,58 @@ def attention(qkv, heads, n_valid=None):
     call("p2pb_vit_attention_forward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(n), ctypes.c_int(n_valid), ptr(qkv),
          ptr(out), stream_ptr())
     return out
+
+
+# ---- the operators of csrc/vit_f16.hip: fp16 matrix operands, fp32 everything else ------------------------------------------
+def _f16_cuda(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor (dinov2 operators have no CPU fallback; the model's CPU path is torch)")
+    if t.dtype != F16 or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous float16 tensor")
+    return t
+
+
+def linear_half(x, weight, bias, gelu=False, residual=None, gamma=None):
+    """x f16[M,K] @ weight f16[N,K]^T + bias f32[N], accumulated in fp32 -> f16[M,N] (rounded once, IEEE); gelu=True: the
+    exact-erf GELU of the fp32 sum, then rounded; residual (f32[M,N], updated IN PLACE and returned) with gamma f32[N]:
+    residual += gamma * (x @ weight^T + bias), all fp32. N % 64 == 0 and K % 32 == 0."""
+    _f16_cuda(x, "x"), _f16_cuda(weight, "weight"), _f32_cuda(bias, "bias")
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1] or bias.shape != (weight.shape[0],) or x.shape[0] < 1:
+        raise ValueError(f"linear_half: x {list(x.shape)}, weight {list(weight.shape)}, bias {list(bias.shape)}")
+    m, k, n = x.shape[0], x.shape[1], weight.shape[0]
+    if n % 64 or k % 32:
+        raise ValueError(f"linear_half: N = {n} must be a multiple of 64 and K = {k} of 32")
+    if (residual is None) != (gamma is None) or (gelu and residual is not None):
+        raise ValueError("linear_half: residual and gamma come together, and not with gelu")
+    if residual is not None:
+        _f32_cuda(residual, "residual"), _f32_cuda(gamma, "gamma")
+        if residual.shape != (m, n) or gamma.shape != (n,):
+            raise ValueError(f"linear_half: residual {list(residual.shape)}, gamma {list(gamma.shape)}")
+    y = residual if residual is not None else torch.empty(m, n, dtype=F16, device=x.device)
+    epi = EPI_RESIDUAL if residual is not None else EPI_GELU if gelu else EPI_BIAS
+    call("p2pb_vit_linear_f16", ctypes.c_int(m), ctypes.c_int(n), ctypes.c_int(k), ptr(x), ptr(weight), ptr(bias), ctypes.c_int(epi),
+         ptr(gamma), ptr(y), stream_ptr())
+    return y
+
+
+def attention_half(qkv, heads, n_valid=None):
+    """`attention` for qkv f16[B, n, 3*heads*64] -> f16[B, n, heads*64]: both products on the matrix pipe, softmax in fp32"""
+    _f16_cuda(qkv, "qkv")
+    if qkv.dim() != 3 or qkv.shape[2] != 3 * heads * HEAD_DIM or qkv.shape[0] < 1 or qkv.shape[1] < 1:
+        raise ValueError(f"attention_half: qkv {list(qkv.shape)} is not [B, n, {3 * heads * HEAD_DIM}]")
+    b, n = qkv.shape[:2]
+    n_valid = n if n_valid is None else int(n_valid)
+    if not 1 <= n_valid <= n:
+        raise ValueError(f"attention_half: n_valid {n_valid} outside [1, {n}]")
+    out = torch.empty(b, n, heads * HEAD_DIM, dtype=F16, device=qkv.device)
+    call("p2pb_vit_attention_forward_f16", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(n), ctypes.c_int(n_valid), ptr(qkv),
+         ptr(out), stream_ptr())
+    return out
+
+
+def _r16(t):
+    """the fp16 rounding of a matrix operand, kept in fp32 (the CPU restatement of the fp16 mode)"""
+    return t.half().float()
 
 
 class _LayerScale(nn.Module):
@@ -149,11 +213,16 @@ class DinoV2(nn.Module):
     """DINOv2 ViT with an MLP block. Parameter names and shapes are those of the published hub checkpoints
     (dinov2_vit{s,b,l}14_pretrain.pth): cls_token [1,1,C], pos_embed [1,1+grid^2,C], mask_token [1,C] (held, unused),
     patch_embed.proj, blocks.{i}.{norm1, attn.qkv (rows (q|k|v) x heads x 64), attn.proj, ls1.gamma, norm2, mlp.fc1, mlp.fc2,
-    ls2.gamma}, norm. Inference only."""
+    ls2.gamma}, norm. Inference only. precision: "fp32" (default) or "fp16" (module docstring, "Arithmetic")."""
+
+    HALF_WEIGHTS = ("attn.qkv", "attn.proj", "mlp.fc1", "mlp.fc2")  # the matrix operands of a block
 
     def __init__(self, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4, patch_size=14, grid=37, layer_norm_eps=1e-6,
-                 interpolate_offset=0.1, ffn_layer="mlp", num_register_tokens=0):
+                 interpolate_offset=0.1, ffn_layer="mlp", num_register_tokens=0, precision="fp32"):
         super().__init__()
+        if precision not in ("fp32", "fp16"):
+            raise ValueError(f"DinoV2: precision {precision!r} is not 'fp32' or 'fp16'")
+        self.precision = precision
         if ffn_layer != "mlp":
             raise ValueError(f"DinoV2: ffn_layer {ffn_layer!r} is not supported (the SwiGLU block of vitg14); only 'mlp'")
         if num_register_tokens != 0:
@@ -167,6 +236,9 @@ class DinoV2(nn.Module):
         self.patch_size, self.grid, self.eps = int(patch_size), int(grid), float(layer_norm_eps)
         self.interpolate_offset = float(interpolate_offset)
         c = self.embed_dim
+        if precision == "fp16" and int(c * mlp_ratio) % 64:
+            raise ValueError(f"DinoV2: precision='fp16' needs an MLP width that is a multiple of 64, not {int(c * mlp_ratio)} "
+                             "(csrc/vit_f16.hip tiles the output channels by 64)")
         self.cls_token = nn.Parameter(torch.zeros(1, 1, c))
         self.pos_embed = nn.Parameter(torch.zeros(1, 1 + self.grid ** 2, c))
         self.mask_token = nn.Parameter(torch.zeros(1, c))
@@ -174,6 +246,7 @@ class DinoV2(nn.Module):
         self.blocks = nn.ModuleList(_Block(c, int(c * mlp_ratio), self.eps) for _ in range(self.depth))
         self.norm = nn.LayerNorm(c, eps=self.eps)
         self._pos_cache = {}
+        self._half_cache = None
         self.requires_grad_(False)
         self.eval()
 
@@ -212,7 +285,20 @@ class DinoV2(nn.Module):
 
     def load_state_dict(self, *args, **kwargs):
         self._pos_cache = {}
+        self._half_cache = None
         return super().load_state_dict(*args, **kwargs)
+
+    def _apply(self, *args, **kwargs):
+        self._half_cache = None  # .to() / .cuda() / .float(): the fp16 weights follow the parameters
+        return super()._apply(*args, **kwargs)
+
+    def half_weights(self):
+        """{"blocks.{i}.{attn.qkv | attn.proj | mlp.fc1 | mlp.fc2}": the weight's `.half()`}: the matrix operands of the fp16
+        mode, made once per model on the parameters' device and kept until `load_state_dict` or `_apply`"""
+        if self._half_cache is None:
+            self._half_cache = {f"blocks.{i}.{name}": blk.get_submodule(name).weight.detach().half().contiguous()
+                                for i, blk in enumerate(self.blocks) for name in self.HALF_WEIGHTS}
+        return self._half_cache
 
     # ---- position embedding -----------------------------------------------------------------------------------------------
     def pos_table(self, h, w, device=None):
@@ -255,6 +341,8 @@ class DinoV2(nn.Module):
         return {"x_norm_clstoken": tok[:, 0], "x_norm_patchtokens": tok[:, 1:]}
 
     def _tokens_torch(self, x, hidden_states=None):
+        if self.precision == "fp16":
+            return self._tokens_torch_half(x, hidden_states)
         b, c, ps = x.shape[0], self.embed_dim, self.patch_size
         hp, wp = x.shape[2] // ps, x.shape[3] // ps
         p = self.patch_embed.proj
@@ -276,6 +364,31 @@ class DinoV2(nn.Module):
                 hidden_states.append(t)
         return F.layer_norm(t, (c,), self.norm.weight, self.norm.bias, self.eps)
 
+    def _tokens_torch_half(self, x, hidden_states=None):
+        """the fp16 mode restated in torch: every matrix operand through .half().float(), products and the rest in fp32"""
+        b, c, ps = x.shape[0], self.embed_dim, self.patch_size
+        hp, wp = x.shape[2] // ps, x.shape[3] // ps
+        p = self.patch_embed.proj
+        t = F.conv2d(x, p.weight, p.bias, stride=ps).flatten(2).transpose(1, 2)
+        t = torch.cat([self.cls_token.expand(b, -1, -1), t], 1) + self.pos_table(hp, wp, x.device)
+        n = t.shape[1]
+        w16 = {k: v.float() for k, v in self.half_weights().items()}
+        if hidden_states is not None:
+            hidden_states.append(t)
+        for i, blk in enumerate(self.blocks):
+            y = _r16(F.layer_norm(t, (c,), blk.norm1.weight, blk.norm1.bias, self.eps))
+            qkv = _r16(F.linear(y, w16[f"blocks.{i}.attn.qkv"], blk.attn.qkv.bias))
+            q, k, v = qkv.view(b, n, 3, self.num_heads, HEAD_DIM).unbind(2)
+            prob = torch.softmax((q * HEAD_DIM ** -0.5).transpose(1, 2) @ k.permute(0, 2, 3, 1), -1)
+            a = _r16((_r16(prob) @ v.transpose(1, 2)).transpose(1, 2).reshape(b, n, c))
+            t = t + blk.ls1.gamma * F.linear(a, w16[f"blocks.{i}.attn.proj"], blk.attn.proj.bias)
+            y = _r16(F.layer_norm(t, (c,), blk.norm2.weight, blk.norm2.bias, self.eps))
+            y = _r16(F.gelu(F.linear(y, w16[f"blocks.{i}.mlp.fc1"], blk.mlp.fc1.bias)))
+            t = t + blk.ls2.gamma * F.linear(y, w16[f"blocks.{i}.mlp.fc2"], blk.mlp.fc2.bias)
+            if hidden_states is not None:
+                hidden_states.append(t)
+        return F.layer_norm(t, (c,), self.norm.weight, self.norm.bias, self.eps)
+
     def _tokens_hip(self, x, hidden_states=None):
         dev = x.device
         b, c, ps = x.shape[0], self.embed_dim, self.patch_size
@@ -287,36 +400,51 @@ class DinoV2(nn.Module):
         ci = ctypes.c_int
         for prm in self.parameters():
             if prm.dtype != F32 or not prm.is_contiguous():
-                raise RuntimeError("DinoV2: parameters must be contiguous float32 (the kernels are fp32)")
+                raise RuntimeError("DinoV2: parameters must be contiguous float32 (precision='fp16' rounds the matrix "
+                                   "operands itself)")
         pos = self.pos_table(hp, wp, dev)
         ws = torch.empty(int(lib().p2pb_vit_patch_embed_ws_floats(ci(b), ci(hp), ci(wp), ci(ps))), dtype=F32, device=dev)
+        half = self.precision == "fp16"
+        act = F16 if half else F32  # the operands of the matrix products: norm outputs, qkv, attention output, hidden
+        if half:
+            w16 = self.half_weights()
+            if w16 and next(iter(w16.values())).device != dev:
+                raise RuntimeError("DinoV2: the cached fp16 weights are not on the model's device")
         t = torch.empty(b, n, c, dtype=F32, device=dev)
-        y = torch.empty(rows, c, dtype=F32, device=dev)
-        qkv = torch.empty(rows, 3 * c, dtype=F32, device=dev)
-        hid = torch.empty(rows, self.blocks[0].mlp.fc1.weight.shape[0], dtype=F32, device=dev) if self.depth else None
+        y = torch.empty(rows, c, dtype=act, device=dev)
+        qkv = torch.empty(rows, 3 * c, dtype=act, device=dev)
+        hid = torch.empty(rows, self.blocks[0].mlp.fc1.weight.shape[0], dtype=act, device=dev) if self.depth else None
         s = stream_ptr()
         p = self.patch_embed.proj
         call("p2pb_vit_patch_embed", ci(b), ci(hp), ci(wp), ci(ps), ci(c), ptr(x), ptr(p.weight), ptr(p.bias),
              ptr(self.cls_token), ptr(pos), ptr(ws), ptr(t), s)
 
         def norm(src, ln, dst):
-            call("p2pb_vit_layernorm", ci(rows), ci(c), ptr(src), ptr(ln.weight), ptr(ln.bias), ctypes.c_float(self.eps),
-                 ptr(dst), s)
+            call("p2pb_vit_layernorm_f16" if dst.dtype == F16 else "p2pb_vit_layernorm", ci(rows), ci(c), ptr(src),
+                 ptr(ln.weight), ptr(ln.bias), ctypes.c_float(self.eps), ptr(dst), s)
 
-        def linear(src, lin, epi, gamma, dst):
-            call("p2pb_vit_linear", ci(rows), ci(lin.weight.shape[0]), ci(lin.weight.shape[1]), ptr(src), ptr(lin.weight),
-                 ptr(lin.bias), ci(epi), ptr(gamma), ptr(dst), s)
+        matmul = "p2pb_vit_linear_f16" if half else "p2pb_vit_linear"
+        attend = "p2pb_vit_attention_forward_f16" if half else "p2pb_vit_attention_forward"
+
+        def linear(src, lin, weight, epi, gamma, dst):
+            call(matmul, ci(rows), ci(weight.shape[0]), ci(weight.shape[1]), ptr(src), ptr(weight), ptr(lin.bias), ci(epi),
+                 ptr(gamma), ptr(dst), s)
 
         if hidden_states is not None:
             hidden_states.append(t.clone())
-        for blk in self.blocks:
+        for i, blk in enumerate(self.blocks):
+            attn, mlp = blk.attn, blk.mlp
+            if half:
+                wq, wp, w1, w2 = (w16[f"blocks.{i}.{name}"] for name in self.HALF_WEIGHTS)
+            else:
+                wq, wp, w1, w2 = attn.qkv.weight, attn.proj.weight, mlp.fc1.weight, mlp.fc2.weight
             norm(t, blk.norm1, y)
-            linear(y, blk.attn.qkv, EPI_BIAS, None, qkv)
-            call("p2pb_vit_attention_forward", ci(b), ci(self.num_heads), ci(n), ci(n), ptr(qkv), ptr(y), s)
-            linear(y, blk.attn.proj, EPI_RESIDUAL, blk.ls1.gamma, t)
+            linear(y, attn.qkv, wq, EPI_BIAS, None, qkv)
+            call(attend, ci(b), ci(self.num_heads), ci(n), ci(n), ptr(qkv), ptr(y), s)
+            linear(y, attn.proj, wp, EPI_RESIDUAL, blk.ls1.gamma, t)
             norm(t, blk.norm2, y)
-            linear(y, blk.mlp.fc1, EPI_GELU, None, hid)
-            linear(hid, blk.mlp.fc2, EPI_RESIDUAL, blk.ls2.gamma, t)
+            linear(y, mlp.fc1, w1, EPI_GELU, None, hid)
+            linear(hid, mlp.fc2, w2, EPI_RESIDUAL, blk.ls2.gamma, t)
             if hidden_states is not None:
                 hidden_states.append(t.clone())
         out = torch.empty(b, n, c, dtype=F32, device=dev)

@@ -3,6 +3,8 @@ Not part of bench.py.
 
   ViT-S/14 forward at 8 x 3 x 182 x 252 (the reference's default batch of 192 x 256 frames, cropped to patch multiples):
       hip            DinoV2.forward_features: 3 + 7 * depth launches, fp32
+      hip fp16       the same weights in a DinoV2(precision="fp16"): fp16 matrix operands on the matrix pipe (csrc/vit_f16.hip),
+                     the arithmetic of the autocast line below; same launch count
       torch fp32     the same weights through F.layer_norm / F.linear / F.scaled_dot_product_attention / F.gelu
       torch fp16 autocast   the same under torch.autocast(float16): what the reference runs (image_features.py:494)
   Feature fusion, 8 frames, 300 000 points, C = 384:
@@ -11,7 +13,7 @@ Not part of bench.py.
     with the peak bytes each allocates on top of its inputs (the map is 8 * 192 * 256 * 384 * 2 = 302 MB, twice while it is
     being made channel-last).
 
-    python tools/bench_dinov2.py [--batch 8] [--points 300000] [--repeats 7] [--window 0.25] [--out profiles/dinov2_timing.txt]
+    python tools/bench_dinov2.py [--batch 8] [--points 300000] [--repeats 7] [--window 0.25] [--out profiles/dinov2_half_timing.txt]
 
 One process, seeded inputs, every variant warmed up, device events around back-to-back calls (as many as fill `window` seconds);
 the variants of a comparison are ALTERNATED inside every repeat; median and minimum per call over the repeats. Needs a GPU."""
@@ -93,6 +95,13 @@ def random_vits(seed):
     return model.cuda()
 
 
+def half_twin(model):
+    """the same weights in an fp16-mode model"""
+    twin = dinov2.dinov2_vits14(precision="fp16")
+    twin.load_state_dict(model.state_dict())
+    return twin.cuda()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
@@ -111,6 +120,7 @@ def main():
 
     b = a.batch
     model = random_vits(0)
+    model16 = half_twin(model)
     gen = torch.Generator(device="cuda").manual_seed(1)
     x = torch.randn(b, 3, H - H % 14, W - W % 14, generator=gen, device="cuda")
     emit({"what": "setup", "model": "ViT-S/14", "input": list(x.shape), "tokens": 1 + (x.shape[2] // 14) * (x.shape[3] // 14),
@@ -118,6 +128,9 @@ def main():
 
     def hip():
         return model.forward_features(x)
+
+    def hip16():
+        return model16.forward_features(x)
 
     @torch.no_grad()
     def torch32():
@@ -130,13 +143,17 @@ def main():
 
     ref = torch32()
     got = torch.cat([hip()["x_norm_clstoken"][:, None], hip()["x_norm_patchtokens"]], 1)
+    got16 = torch.cat([hip16()["x_norm_clstoken"][:, None], hip16()["x_norm_patchtokens"]], 1)
     emit({"what": "agreement", "max_abs_hip_minus_torch_fp32": float((got - ref).abs().max()),
-          "max_abs_autocast_minus_torch_fp32": float((torch16().float() - ref).abs().max()), "rms": float(ref.pow(2).mean().sqrt())})
+          "max_abs_autocast_minus_torch_fp32": float((torch16().float() - ref).abs().max()),
+          "max_abs_hip_fp16_minus_torch_fp32": float((got16 - ref).abs().max()), "rms": float(ref.pow(2).mean().sqrt())})
     res = compare([("vit-s forward hip fp32", hip), ("vit-s forward torch fp32", torch32),
-                   ("vit-s forward torch fp16 autocast", torch16)], a.repeats, a.window)
+                   ("vit-s forward torch fp16 autocast", torch16), ("vit-s forward hip fp16", hip16)], a.repeats, a.window)
     for r in res:
         r["ms_per_frame_at_median"] = r["ms_median"] / b
         r["relative_to_hip"] = r["ms_median"] / res[0]["ms_median"]
+    res[3]["relative_to_torch_fp16_autocast"] = res[3]["ms_median"] / res[2]["ms_median"]
+    for r in res:
         emit(r)
 
     # ---- fusion ------------------------------------------------------------------------------------------------------
