@@ -509,7 +509,7 @@ int p2pb_pvconv_tail(int b, int c, int hidden, const float *part2, int nslots2, 
                      int style_stridep, float epsp, float *scale_p, float *shift_p, void *stream);
 
 /* Voxel-major forms for the fused branch (grid f32[b,r,r,r,c]; conv flags bit 3): same values as
- * p2pb_avg_voxelize_forward / p2pb_trilinear_devoxelize_affine, coalesced on both sides (voxelize.hip).
+ * p2pb_avg_voxelize_forward / p2pb_trilinear_devoxelize_affine, coalesced on both sides (voxel_gather.hip, devoxelize.hip).
  * feat_t: f32[b,n,c] scratch (the point-major copy of feat); aff_a/aff_b may both be NULL. With add:
  * outs += swish(add*add_scale[b,c] + add_shift[b,c]), PVConv's point branch (models/pvcnn.py:286,325). */
 int p2pb_avg_voxelize_cl_forward(int b, int c, int n, int r, const int *coords, const float *feat, int *ind, int *cnt,

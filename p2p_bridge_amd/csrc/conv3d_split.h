@@ -173,7 +173,7 @@ __device__ __forceinline__ void split_taps_pre(f32x16 (&acc)[NT], const u32x4 *_
 // order [chunk][plane][khalf][voxel] -- 160-byte runs per DMA instruction instead of one cache line per lane -- was built
 // and measured: the convolutions alone 6 % faster, the bench 1.4 % SLOWER, because both producers then write through an
 // LDS transpose or read strided; profiles/README.md.) Producers:
-// the voxeliser for a first convolution (voxelize.hip vox_gather_cl_split_kernel: no extra pass), conv3d_presplit_kernel for
+// the voxeliser for a first convolution (voxel_gather.hip vox_gather_cl_split_kernel: no extra pass), conv3d_presplit_kernel for
 // a second one (one elementwise pass over y1 once its GroupNorm statistics are folded). Same transform, same split, same
 // products in the same order as the staging code below: outputs are bit-identical to the PRE = false kernels.
 // The stage loop is double-buffered (2 x 37.5 KB, two workgroups per CU) with ONE barrier per stage: wait for my DMA of

@@ -126,7 +126,7 @@ extern "C" int p2pb_minmax_act_pool_gn(int b, int c, int nslots, const float *mi
 // per-sample bias (models/pvcnn.py:926) -- are weight-streaming GEMVs (54 MB of weights for the styles). They used to go
 // through torch's BLAS, whose per-stream WORKSPACE a captured graph bakes in: two sampler chains replaying their graphs side
 // by side then shared one workspace and corrupted each other's GEMMs (round 4, tests/test_full_size_parity_gpu.py::
-// test_c2_bench_dispatch_two_chains_b32 -- the corruption found there turned out to be the devoxelisation's, voxelize.hip; the
+// test_c2_bench_dispatch_two_chains_b32 -- the corruption found there turned out to be the devoxelisation's, devoxelize.hip; the
 // workspace sharing is real all the same).
 // This kernel needs no scratch: the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32: fp32 products, fp32 accumulate) with
 // M = 32 weight rows, N = the batch rows (<= 16 per chunk, x staged in LDS with a 4-float row pad: conflict-free 16-byte reads),

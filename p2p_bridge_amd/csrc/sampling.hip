@@ -587,7 +587,7 @@ __global__ __launch_bounds__(1024) void fps_grid_kernel(int n, int m, const floa
     if (key == wkey && (wkey != 0 ? true : lane == 0)) {  // (an all-empty wave: lane 0 writes the zero key)
       slots[j & 1][wave] = wkey;
       // (one 16-byte store: three adjacent floats become a ds_write_b96, which misbehaved beside another stream's matrix
-      //  kernels -- voxelize.hip devox_cl_kernel, round 4)
+      //  kernels -- devoxelize.hip devox_stage_corners, round 4)
       *(volatile fg_f32x4 *)&sxyz[j & 1][wave][0] = fg_f32x4{kx, ky, kz, 0.0f};
     }
     __syncthreads();

@@ -1,4 +1,4 @@
-"""Inference-time fused voxel branch of PVConv on the gfx950 kernels (csrc/conv3d.hip, voxelize.hip).
+"""Inference-time fused voxel branch of PVConv on the gfx950 kernels (csrc/conv3d.hip, voxel_coords.hip, voxel_gather.hip, devoxelize.hip).
 
     voxel grid --conv3d+stats--> y1 --[GN+AdaGN -> affine]--> conv3d(affine+Swish on load)+stats --> y2
                --[GN+AdaGN -> affine, SE gate from channel means]--> devoxelize(affine on load)

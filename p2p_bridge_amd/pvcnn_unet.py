@@ -536,7 +536,7 @@ class PVConv(nn.Module):
         geo_v = geo.take_voxel(self.level, r) if (geo is not None and self.level >= 0) else None
         lists = counts = None
         # the grids of this branch are voxel-major [B,r,r,r,C]: contiguous channels for the convolutions' staging
-        # loads and stores, and coalesced voxelize / devoxelize (csrc/voxelize.hip)
+        # loads and stores, and coalesced voxelize / devoxelize (csrc/voxel_gather.hip, devoxelize.hip)
         # pre-split operand grids (fused.conv_pre_plan): the voxeliser writes the first convolution's operand already
         # split, one elementwise pass does the same for the second one -- the convolutions then stage with LDS-DMA alone
         pre1 = pre2 = False

@@ -202,7 +202,7 @@ def test_pw_conv_pool_gather(arena, fused, B, N, M, U, Ci, Co, with_fin):
         assert rel_err(got, swish(out * sc2[:, :, None, None].double() + sh2[:, :, None, None].double()).amax(-1)) < TOL
 
 
-# ---- 3. voxel_sort / voxelize_cl_gather (csrc/voxelize.hip; bit-exact against the oracle) --------------------------------
+# ---- 3. voxel_sort / voxelize_cl_gather (csrc/voxel_coords.hip, voxel_gather.hip; bit-exact against the oracle) --------------------------------
 
 # (B, C, N, r, seed of the cloud). Arms of p2pb_avg_voxelize_cl_gather (fp32 grid) | p2pb_avg_voxelize_cl_gather_split:
 #   (2, 35, 301, 4)  : C % 4 != 0: zero-fill + vox_gather_cl_occ_kernel | zero-fill + vox_gather_cl_occ_split_kernel<false>; the
@@ -218,6 +218,8 @@ def test_pw_conv_pool_gather(arena, fused, B, N, M, U, Ci, Co, with_fin):
 #   (2, 64, 128, 8)  : r^3 = 512 >= 4 N: vox_gather_cl_all_kernel<true> | zero-fill + vox_gather_cl_occ_split_kernel<true>
 #   (1, 36, 1000, 16): r^3 = 4096 >= 4 N, C = 36 (three chunks, the last one padded by twelve channels, its second thread
 #                      without channels): vox_gather_cl_all_kernel<true> | vox_gather_cl_occ_split_kernel<true>
+# The arms only an A/B switch reaches (vox_gather_cl_all_kernel<false>, vox_gather_cl_split_kernel<false>, the occupied forms on
+# 16-byte rows at r^3 < 4 N): tests/test_voxel_switch_arms_gpu.py runs this file's test on the first five shapes with the switch set.
 VOX_SHAPES = [(2, 35, 301, 4, 0), (1, 16, 64, 4, 2), (2, 12, 257, 4, 0), (2, 64, 130, 8, 0), (2, 64, 128, 8, 0), (1, 36, 1000, 16, 0)]
 
 

@@ -1,6 +1,6 @@
 """The point-major gather / scatter-back kernels of the sampler's critical stream issue their independent loads per batch
-(csrc/neighbors.hip group_stats_kernel, group_sub_kernel, three_interp_add_kernel; csrc/voxelize.hip devox_cl_kernel,
-devox_cl4_kernel; from the audit of the other small kernels: vox_gather_cl_split_kernel, far_field_kernel and the SE3d
+(csrc/neighbors.hip group_stats_kernel, group_sub_kernel, three_interp_add_kernel; csrc/devoxelize.hip devox_cl_kernel,
+devox_cl4_kernel; from the audit of the other small kernels: csrc/voxel_gather.hip vox_gather_cl_split_kernel, far_field_kernel and the SE3d
 bottleneck se_hidden of pvconv_tail_kernel / se_gate_affine_kernel: profiles/r07_gather_wait_audit.txt). Only the ORDER OF
 THE LOADS may differ from the kernels before that change: every output bit is held to what the previous kernels wrote,
 recorded once by tools/make_golden_gather_tails.py (run on the GPU with the library of the commit before the change) in
@@ -33,7 +33,7 @@ TI_C = [3, 64, 72, 128]
 DV_B = 2
 DV_R = [4, 8]
 DV_N = [1, 63, 65, 130]
-DV_C = [3, 35, 64, 128]  # devox_cl (3, 35) and devox_cl4 (64, 128)
+DV_C = [3, 35, 64, 128]  # devox_cl (3, 35) and devox_cl4 (64, 128; devox_cl there: test_voxel_switch_arms_gpu.py)
 VG_B, VG_R = 2, 4  # 64 voxels: the one-pass split gather runs where a cloud has more than a quarter point per voxel
 VG_N = [20, 130, 257]  # empty voxels, voxels of 1 .. 67 points: ragged and whole batches of four points
 VG_C = [4, 12, 36, 64]  # multiples of 4 (16-byte rows), ragged against the 8-channel thread and the 16-channel chunk

@@ -13,7 +13,8 @@ Wrappers of fused.py that no case calls here are held in tests/test_fused_discip
 references only: interp_add, pw_conv_pool_gather, voxel_sort / voxelize_cl_gather, conv3d_presplit and the `pre=True`
 convolutions, conv3d_far_field_gn, pvconv_tail, minmax_act_pool_gn, affine_act, and the arms this file passes by (pw_conv's
 point_major / ci_lo, ci_hi / fin= / wide-layer pre-pass, devoxelize_affine's add=, minmax_act and affine_act_max on host-built
-inputs). Still NOT held of fused.py: no wrapper that launches a kernel; operand_audit is a diagnostic around the wrappers
+inputs); the arms of the voxel gathers and of the channels-last devoxelize that only an A/B switch reaches, in
+tests/test_voxel_switch_arms_gpu.py. Still NOT held of fused.py: no wrapper that launches a kernel; operand_audit is a diagnostic around the wrappers
 above whose own arithmetic is torch's.
 
 Run time on an MI355X: 111 cases in 9.3 s on their own; the whole `-m gpu` suite took 293.9 s with this file in it (710 tests),

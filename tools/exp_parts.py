@@ -1,5 +1,5 @@
 """Stand-alone timings of small kernels of an evaluation at the bench's shapes (B = 16 and 32): the styles' linear_rows, the r = 32
-voxelisation, far_field. usage: python tools/exp_parts.py [P2PB_LIB_PATH=...]"""
+voxelisation, the channels-last devoxelisation, far_field. usage: python tools/exp_parts.py [P2PB_LIB_PATH=...]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from p2p_bridge_amd import fused, pointnet2_batch_cuda as ext
@@ -37,3 +37,10 @@ for B in (16, 32):
         f = torch.randn(B, C, 8192, device="cuda")
         t = timeit(lambda: fused.voxelize_cl_gather(f, cnt, ws, r, split=True))
         print(f"B={B} voxelize_cl_gather(split) r={r} C={C}: {t:.1f} us")
+    for r, C, N in ((32, 64, 8192), (32, 35, 8192), (16, 128, 2048)):  # devox_cl4 / devox_cl (C % 64 != 0) with the point branch
+        vc, _ = ext.voxel_coords(pts[:, :, :N].contiguous(), r)
+        grid = torch.randn(B, r, r, r, C, device="cuda")
+        a, b_, hs, hb = (torch.randn(B, C, device="cuda") for _ in range(4))
+        h = torch.randn(B, C, N, device="cuda")
+        t = timeit(lambda: fused.devoxelize_affine(grid, vc, r, a, b_, channels_last=True, add=(h, hs, hb)))
+        print(f"B={B} devoxelize_affine(channels_last, add) r={r} C={C} N={N}: {t:.1f} us")
