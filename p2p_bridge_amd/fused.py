@@ -735,6 +735,12 @@ def affine_act(x, scale, shift, swish=True, residual=None):
     return y
 
 
+def act_max_supported(m: int, u: int) -> bool:
+    """does affine_act_max take this plane? (csrc/pointwise_act.hip p2pb_affine_act_max: u a power of two <= 64 over whole
+    waves, (m * u) % 64 == 0 -- or u == 0, the whole row; it refuses every other plane before it launches anything)"""
+    return u == 0 or (u > 0 and (u & (u - 1)) == 0 and u <= 64 and (m * u) % 64 == 0)
+
+
 def affine_act_max(x, scale, shift, m, u, swish=True):
     """max over the last (neighbour) axis of swish(x*scale+shift): x f32[B,C,m*u] -> f32[B,C,m];
     u == 0: max over the whole row -> f32[B,C]"""

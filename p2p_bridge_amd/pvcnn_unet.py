@@ -459,12 +459,23 @@ class SharedMLP(nn.Module):
             h = h.contiguous()
         sc = sh = None
         nl = len(self.layers) // 3
+
+        def act_max(h, sc, sh):
+            # max over the neighbour axis of Swish(norm(h)). A plane affine_act_max refuses (a neighbourhood size that is no
+            # power of two, m * u no multiple of 64) takes two launches: the folded norm + Swish, then the row maximum
+            m, u, C = int(np.prod(shape[2:-1])), shape[-1], h.shape[1]
+            if fused.act_max_supported(m, u):
+                return fused.affine_act_max(h, sc, sh, m, u).view(B, C, *shape[2:-1])
+            from . import dense
+
+            return dense.row_max(fused.affine_act(h, sc, sh, True, None).view(B, C, m, u)).view(B, C, *shape[2:-1])
+
         if first is not None:
             sc, sh = norm_affine(self.layers[1], first, P, cond)
             if nl == 1:
                 C = h.shape[1]
                 if reduce_max:
-                    return fused.affine_act_max(h, sc, sh, int(np.prod(shape[2:-1])), shape[-1]).view(B, C, *shape[2:-1])
+                    return act_max(h, sc, sh)
                 return fused.affine_act(h, sc, sh, True, None).view(B, C, *shape[2:])
         # set abstraction: the last layer's output is only ever max-pooled over the neighbour axis, so its
         # GEMM emits per-neighbourhood {min, max} instead of the tensor (fused.pw_conv pool_u)
@@ -478,7 +489,7 @@ class SharedMLP(nn.Module):
             h, st, (sc, sh, _) = fused.pw_conv(h, conv, sc, sh, swish=sc is not None, fin=norm_fin(norm, P, cond))
         C = h.shape[1]
         if reduce_max:
-            return fused.affine_act_max(h, sc, sh, int(np.prod(shape[2:-1])), shape[-1]).view(B, C, *shape[2:-1])
+            return act_max(h, sc, sh)
         res = None if residual is None else residual.reshape(B, C, P)
         return fused.affine_act(h, sc, sh, True, res).view(B, C, *shape[2:])
 
@@ -714,11 +725,12 @@ class PointNetSAModule(nn.Module):
             mlp = self.mlps[0]
             from . import fused
 
-            if fused.enabled(mlp, coords) and data.features is not None:
+            if fused.enabled(mlp, coords):
                 # the first 1x1 convolution commutes with the grouping (linear): run it on the N points, then gather
                 # its C1-channel output and subtract the centre term (csrc/neighbors.hip group_sub_kernel)
                 conv0 = mlp.layers[0]
-                xin = torch.cat([coords, data.features], dim=1)
+                # (no features: the relative coordinates alone, as BallQuery.forward groups them)
+                xin = coords.contiguous() if data.features is None else torch.cat([coords, data.features], dim=1)
                 cen = centers.contiguous()
                 pm = xin.shape[2] % 4 == 0 and cen.shape[2] % 4 == 0  # both GEMMs can write point-major rows
                 z, _ = fused.pw_conv(xin, conv0, stats=False, point_major=pm)
@@ -737,6 +749,9 @@ class PointNetSAModule(nn.Module):
                 else:
                     y, st = fused.group_sub(z, cx, nidx, point_major=pm)
                     data.features = mlp._run_fused(y.view(y.shape[0], y.shape[1], M, U), data.cond, True, None, first=st)
+            elif data.features is None:
+                grouped = L.pvcnn_grouping(coords.contiguous(), nidx) - centers.unsqueeze(-1)
+                data.features = mlp.run(grouped, data.cond, reduce_max=True)
             else:
                 grouped = L._ext.group_concat(coords.contiguous(), centers, data.features.contiguous(), nidx)
                 data.features = mlp.run(grouped, data.cond, reduce_max=True)
