@@ -50,6 +50,13 @@ def get_int(key, default):
     return int(v) if v not in (None, "") else default
 
 
+def resolution_pair(key, default):
+    """a "first:second" value such as "32,16:16" -> (set of first resolutions, set of second ones): which voxel resolutions put
+    the first / second convolution of a PVConv into some form (pvcnn_unet.compact_plan, fused.conv_pre_plan); "" = neither"""
+    parts = (get(key, default).split(":") + [""])[:2]
+    return tuple({int(t) for t in p.split(",") if t.strip()} for p in parts)
+
+
 def setting(**kv):
     """the P2PB_EXPERIMENT string with `kv` merged in (None removes a key): for tests / tools that build an environment"""
     t = _table()

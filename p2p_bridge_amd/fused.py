@@ -178,9 +178,7 @@ def conv_pre_plan(r: int):
     P2PB_EXPERIMENT="conv_pre=<first>:<second>" lists resolutions, default below; f16x3 arithmetic only."""
     if conv_math() != "f16x3" or lib().p2pb_get_split_terms() != 16:
         return False, False
-    spec = _experiment.get("conv_pre", CONV_PRE_DEFAULT)
-    parts = (spec.split(":") + [""])[:2]
-    first, second = ({int(t) for t in q.split(",") if t.strip()} for q in parts)
+    first, second = _experiment.resolution_pair("conv_pre", CONV_PRE_DEFAULT)
     return int(r) in first, int(r) in second
 
 
@@ -198,6 +196,25 @@ def conv3d_presplit(y, in_scale=None, in_shift=None, swish=False, in_sub=None):
     return out
 
 
+def _conv3d_prologue(x, conv, split, channels_last, pre, in_scale, in_sub, stats=True):
+    """what the three voxel-convolution wrappers below do before their launch -> (b, ci, co, r, packed weight, y, statistics
+    partials | None). pre: x is the pre-split operand grid of conv3d_presplit / voxelize_cl_gather(split=True) -- split
+    arithmetic, voxel-major, nothing left to apply on load"""
+    check(x, F32, "x")
+    b, ci, r = (x.shape[0], x.shape[4], x.shape[1]) if channels_last else (x.shape[0], x.shape[1], x.shape[2])
+    co = conv.out_channels
+    if pre:
+        assert split and channels_last and in_scale is None and in_sub is None and x.shape[4] == (conv.in_channels + 15) // 16 * 16
+        ci = conv.in_channels
+    wt = pack_conv3d_weight(conv, split)
+    y = torch.empty(*((b, r, r, r, co) if channels_last else (b, co, r, r, r)), dtype=F32, device=x.device)
+    st = None
+    if stats:
+        nfl = lib().p2pb_conv3d_k3_stats_floats(_i(b), _i(co), _i(r))
+        st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
+    return b, ci, co, r, wt, y, st
+
+
 @_honours_pin(1)
 def conv3d_k3(x, conv, in_scale=None, in_shift=None, swish=False, stats=True, in_sub=None, out_class=None,
               skip_zero=False, compact=False, math=None, force_split=False, channels_last=False, pre=False):
@@ -205,19 +222,8 @@ def conv3d_k3(x, conv, in_scale=None, in_shift=None, swish=False, stats=True, in
     channels_last the grids are voxel-major, x f32[B,r,r,r,Cin] -> y f32[B,r,r,r,Cout] (the layout of the fused
     voxel branch: contiguous channels for the staging loads, the stores, voxelize and devoxelize).
     in_sub / out_class / skip_zero / compact: the exact sparse form (csrc/conv3d.hip header)."""
-    check(x, F32, "x")
-    b, ci, r = (x.shape[0], x.shape[4], x.shape[1]) if channels_last else (x.shape[0], x.shape[1], x.shape[2])
-    co = conv.out_channels
-    split = force_split or use_split(co, math)
-    if pre:  # x is the pre-split operand grid of conv3d_presplit / voxelize_cl_gather(split=True)
-        assert split and channels_last and in_scale is None and in_sub is None and x.shape[4] == (conv.in_channels + 15) // 16 * 16
-        ci = conv.in_channels
-    wt = pack_conv3d_weight(conv, split)
-    y = torch.empty((b, r, r, r, co) if channels_last else (b, co, r, r, r), dtype=F32, device=x.device)
-    st = None
-    if stats:
-        nfl = lib().p2pb_conv3d_k3_stats_floats(_i(b), _i(co), _i(r))
-        st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
+    split = force_split or use_split(conv.out_channels, math)
+    b, ci, co, r, wt, y, st = _conv3d_prologue(x, conv, split, channels_last, pre, in_scale, in_sub, stats)
     flags = (1 if skip_zero else 0) | (2 if compact else 0) | (4 if split else 0) | (8 if channels_last else 0) | (16 if pre else 0)
     call("p2pb_conv3d_k3_forward_ex", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias), ptr(out_class),
          ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(in_sub), _i(flags), ptr(y), ptr(st), stream_ptr())
@@ -243,17 +249,8 @@ def conv3d_k3_sparse(x, conv, lists, counts, which, in_scale=None, in_shift=None
     pre: x is the pre-split operand grid (conv3d_presplit / voxelize_cl_gather(split=True));
     active_only: the outputs of the inactive bricks are left UNWRITTEN (their statistics are still exact) -- for a caller
     that reads y inside the active bricks only, e.g. the devoxelisation behind a PVConv's second convolution"""
-    check(x, F32, "x")
-    b, ci, r = (x.shape[0], x.shape[4], x.shape[1]) if channels_last else (x.shape[0], x.shape[1], x.shape[2])
-    co = conv.out_channels
-    split = use_split(co, math)
-    if pre:
-        assert split and channels_last and in_scale is None and in_sub is None and x.shape[4] == (conv.in_channels + 15) // 16 * 16
-        ci = conv.in_channels
-    wt = pack_conv3d_weight(conv, split)
-    y = torch.empty((b, r, r, r, co) if channels_last else (b, co, r, r, r), dtype=F32, device=x.device)
-    nfl = lib().p2pb_conv3d_k3_stats_floats(_i(b), _i(co), _i(r))
-    st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
+    split = use_split(conv.out_channels, math)
+    b, ci, co, r, wt, y, st = _conv3d_prologue(x, conv, split, channels_last, pre, in_scale, in_sub)
     act, ina = lists[2 * which], lists[2 * which + 1]
     ca, ci_ = counts[2 * which:], counts[2 * which + 1:]
     flags = (4 if split else 0) | (8 if channels_last else 0) | (16 if pre else 0) | (32 if active_only else 0)
@@ -283,17 +280,10 @@ def conv3d_k3_compact(x, conv, lists, counts, which, in_scale=None, in_shift=Non
     far-field form (set D2; in_sub / out_class from conv3d_far_field). x f32[B,r,r,r,Cin] -> (y f32[B,r,r,r,Cout], stats).
     listed_only: y is left UNWRITTEN outside the listed voxels (the statistics stay exact) -- for a caller that reads y inside
     the set alone (a PVConv's second convolution: the devoxelisation's corners lie within one voxel of an occupied voxel)"""
-    check(x, F32, "x")
-    b, r, ci = x.shape[0], x.shape[1], x.shape[4]
-    co = conv.out_channels
-    wt = pack_conv3d_weight(conv, True)
-    y = torch.empty(b, r, r, r, co, dtype=F32, device=x.device)
-    nfl = lib().p2pb_conv3d_k3_stats_floats(_i(b), _i(co), _i(r))
-    st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
+    b, ci, co, r, wt, y, st = _conv3d_prologue(x, conv, True, True, pre, in_scale, in_sub)
     al, ac = lists[which], counts[which]
-    if pre:  # x is the pre-split operand grid
-        assert in_scale is None and in_sub is None and x.shape[4] == (conv.in_channels + 15) // 16 * 16
-        call("p2pb_conv3d_k3_forward_compact_pre", _i(b), _i(conv.in_channels), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias),
+    if pre:
+        call("p2pb_conv3d_k3_forward_compact_pre", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias),
              ptr(out_class), ptr(al), ptr(ac), ptr(y), ptr(st), _i(32 if listed_only else 0), stream_ptr())
         return y, st
     call("p2pb_conv3d_k3_forward_compact", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias),

@@ -515,7 +515,9 @@ class Voxelization(nn.Module):
 
 class PVConv(nn.Module):
     """voxel branch (voxelize -> Conv3d, AdaGN, Swish, Dropout, Conv3d, AdaGN, SE3d -> trilinear
-    devoxelize) + point branch (SharedMLP), summed (models/pvcnn.py:237-334)."""
+    devoxelize) + point branch (SharedMLP), summed (models/pvcnn.py:237-334). Inference at a resolution of FUSED_RESOLUTIONS runs
+    _voxel_branch_fused, one straight line whose two convolutions take the forms voxel_conv_plan names; anything else the HIP
+    forward + backward of dense.py."""
 
     def __init__(self, in_channels, out_channels, resolution, with_se=True, dropout=0.1, gn_groups=8, cond_dim=0,
                  normalize=True, eps=0.0, attention=None):
@@ -530,7 +532,7 @@ class PVConv(nn.Module):
         self.voxel_layers = nn.ModuleList(mods)
         # attention: a LinearAttention factory when the config's `attentions` flags this block (models/pvcnn.py:293-296)
         self.attn = attention(out_channels) if attention is not None else None
-        self.sparse_conv = True  # inference: exact sparse convolution for r >= 16 (fused._voxel_branch_fused)
+        self.sparse_conv = True  # inference: the exact sparse convolution forms where voxel_conv_plan has one; False: dense
         self.level = -1  # set by PVCNN2Unet: index of the coordinate level this block works on (Geometry.take_voxel)
         self.point_features = SharedMLP(in_channels, out_channels, gn_groups=gn_groups, cond_dim=cond_dim)
         # set by PVCNN2Unet: the per-pass state it shares with its blocks ({"drop_seed": int32[2] | None}) and this block's
@@ -538,98 +540,69 @@ class PVConv(nn.Module):
         self._pass, self.drop_salt = None, 0
 
     def _voxel_branch_fused(self, features, coords, cond, point=None, geo=None):
-        """inference: voxelize -> conv -> [AdaGN,Swish folded] -> conv -> [AdaGN,SE folded] -> devoxelize; grid
-        tensors written once / read once (fused.py). For r >= 16 the convolutions run in their exact sparse form:
-        MFMA work only on the bricks near the surface, analytic constants elsewhere (csrc/conv3d.hip)."""
+        """inference: voxelize -> conv -> [AdaGN,Swish folded] -> conv -> [AdaGN,SE folded] -> devoxelize; grid tensors written
+        once / read once (fused.py). Each convolution runs in the form voxel_conv_plan names: for r >= 16 the exact sparse forms,
+        MFMA work only near the surface, analytic constants elsewhere (csrc/conv3d.hip).
+        point = (h, partials, norm): the point branch's raw conv output, its statistics and the norm that follows -- its Swish and
+        the sum of the two branches then happen in the devoxelisation pass; None: the voxel branch alone"""
         from . import fused
 
         vl, r = self.voxel_layers, self.resolution
-        geo_v = geo.take_voxel(self.level, r) if (geo is not None and self.level >= 0) else None
+        form1, form2, kind = voxel_conv_plan(r, self.sparse_conv)
         lists = counts = None
         # the grids of this branch are voxel-major [B,r,r,r,C]: contiguous channels for the convolutions' staging
         # loads and stores, and coalesced voxelize / devoxelize (csrc/voxel_gather.hip, devoxelize.hip)
         # pre-split operand grids (fused.conv_pre_plan): the voxeliser writes the first convolution's operand already
         # split, one elementwise pass does the same for the second one -- the convolutions then stage with LDS-DMA alone
         pre1 = pre2 = False
-        if geo_v is not None:  # coordinate-only half (voxel coordinates, sort, brick lists) came from the geometry stream
-            vcoords, cnt, ws, lists, counts = geo_v
+        geo_v = geo.take_voxel(self.level, r) if (geo is not None and self.level >= 0) else None
+        if geo_v is not None:  # coordinate-only half (voxel coordinates, sort, lists) came from the geometry stream
+            vcoords, cnt, ws, have, lists, counts = geo_v
+            if have != kind:  # lists of another kind (shape, dtype) than this block's plan reads: never indexed
+                lists = counts = None
             pre1, pre2 = fused.conv_pre_plan(r)
             # (a layer pinned to bf16x6 -- fused.pin_layer_math, P2PB.calibrate_ranges -- takes its operand as fp32)
             pre1, pre2 = pre1 and fused.pinned_math(vl[0]) is None, pre2 and fused.pinned_math(vl[4]) is None
             v = fused.voxelize_cl_gather(features.contiguous(), cnt, ws, r, split=pre1)
         else:
-            vcoords, vox = L.voxel_coords(coords.detach().contiguous(), r, self.voxelization.normalize,
-                                          self.voxelization.eps)
+            vcoords, vox = L.voxel_coords(coords.detach().contiguous(), r, self.voxelization.normalize, self.voxelization.eps)
             v, cnt = fused.voxelize_cl(features.contiguous(), vox, r)
+        if kind is not None and lists is None:
+            lists, counts = _voxel_lists(kind, cnt, r)
         r3 = float(r ** 3)
-        c1, c2 = compact_plan()
-        if self.sparse_conv and (r in c1 or r in c2):
-            # voxel-level sparsity: only the outputs within one (first conv) / two (second conv, far-field form) voxels
-            # of an occupied voxel are computed, packed densely into the MFMA column tiles
-            if lists is None:
-                lists, counts = fused.active_lists(cnt, r)
-            if r in c1:
-                y1, st1 = fused.conv3d_k3_compact(v, vl[0], lists, counts, 0, pre=pre1)
-            else:
-                y1, st1 = fused.conv3d_k3(v, vl[0], compact=True, channels_last=True, pre=pre1)
-            if r in c2:  # (the norm between the convolutions is folded inside the far-field launch)
-                sc1, sh1, a, k = fused.conv3d_far_field_gn(vl[0].bias, vl[4], st1, norm_fin(vl[1], r3, cond), True)
-                if pre2:
-                    # (listed_only: y2 is read by the devoxelisation alone -- corners within one voxel of an occupied voxel, inside D1)
-                    y2, st2 = fused.conv3d_k3_compact(fused.conv3d_presplit(y1, sc1, sh1, True, a), vl[4], lists, counts, 1,
-                                                      out_class=k, pre=True, listed_only=True)
-                else:
-                    y2, st2 = fused.conv3d_k3_compact(y1, vl[4], lists, counts, 1, sc1, sh1, True, in_sub=a, out_class=k,
-                                                      listed_only=True)
-            else:
-                sc1, sh1 = norm_affine(vl[1], st1, r3, cond)
-                if pre2:
-                    y2, st2 = fused.conv3d_k3(fused.conv3d_presplit(y1, sc1, sh1, True), vl[4], compact=True, channels_last=True, pre=True)
-                else:
-                    y2, st2 = fused.conv3d_k3(y1, vl[4], sc1, sh1, swish=True, compact=True, channels_last=True)
-        elif r >= 32 and self.sparse_conv:  # at r = 16 every 4x8x8 brick touches the surface: dense is faster
-            if lists is None:
-                lists, counts = fused.brick_lists(cnt, r)
-            y1, st1 = fused.conv3d_k3_sparse(v, vl[0], lists, counts, 0, channels_last=True, pre=pre1)
-            sc1, sh1, a, k = fused.conv3d_far_field_gn(vl[0].bias, vl[4], st1, norm_fin(vl[1], r3, cond), True)
-            if pre2:
-                y2, st2 = fused.conv3d_k3_sparse(fused.conv3d_presplit(y1, sc1, sh1, True, a), vl[4], lists, counts, 1,
-                                                 out_class=k, channels_last=True, pre=True, active_only=True)
-            else:  # (y2 is read by the devoxelisation alone: corners within one voxel of an occupied voxel = active bricks)
-                y2, st2 = fused.conv3d_k3_sparse(y1, vl[4], lists, counts, 1, sc1, sh1, True, in_sub=a, out_class=k,
-                                                 channels_last=True, active_only=True)
+        y1, st1 = _voxel_conv(form1, v, vl[0], lists, counts, 0, pre=pre1)
+        a = k = None
+        if form2 != "dense":  # far-field form; the norm between the convolutions is folded inside the far-field launch
+            sc, sh, a, k = fused.conv3d_far_field_gn(vl[0].bias, vl[4], st1, norm_fin(vl[1], r3, cond), True)
         else:
-            y1, st1 = fused.conv3d_k3(v, vl[0], compact=True, channels_last=True, pre=pre1)
-            sc1, sh1 = norm_affine(vl[1], st1, r3, cond)
-            if pre2:
-                y2, st2 = fused.conv3d_k3(fused.conv3d_presplit(y1, sc1, sh1, True), vl[4], compact=True, channels_last=True, pre=True)
-            else:
-                y2, st2 = fused.conv3d_k3(y1, vl[4], sc1, sh1, swish=True, compact=True, channels_last=True)
+            sc, sh = norm_affine(vl[1], st1, r3, cond)
+        if pre2:
+            x2, on_load = fused.conv3d_presplit(y1, sc, sh, True, a), {}
+        else:
+            x2, on_load = y1, dict(in_scale=sc, in_shift=sh, swish=True, in_sub=a)
+        # (y2 is read by the devoxelisation alone -- corners within one voxel of an occupied voxel: inside D1 / the active bricks)
+        y2, st2 = _voxel_conv(form2, x2, vl[4], lists, counts, 1, out_class=k, pre=pre2, unread_unwritten=True, **on_load)
         se = vl[6] if len(vl) > 6 else None
-        # the second norm (+ channel means), the SE3d gate and the point branch's norm in ONE launch (fused.pvconv_tail);
-        # point = (h, partials, norm): the point branch's raw conv output, its statistics and the norm that follows; its Swish
-        # and the sum of the two branches happen in the devoxelisation pass
+        # the second norm (+ channel means), the SE3d gate and the point branch's norm in ONE launch
         aff_a, aff_b, scp, shp = fused.pvconv_tail(st2, norm_fin(vl[5], r3, cond), None if se is None else (se.fc[0].weight, se.fc[2].weight),
                                                    None if point is None else (point[1], point[2]))
-        return fused.devoxelize_affine(y2, vcoords, r, aff_a, aff_b, channels_last=True,
-                                       add=None if point is None else (point[0], scp, shp))
+        return fused.devoxelize_affine(y2, vcoords, r, aff_a, aff_b, channels_last=True, add=None if point is None else (point[0], scp, shp))
 
     def forward(self, data: PVCData) -> PVCData:
+        """every arm leaves either `out` (the block's output) or what the point branch adds to its own: `residual` [, `gate`]"""
         coords, features, cond = data.coords, data.features, data.cond
         assert features.shape[0] == coords.shape[0] and features.shape[2] == coords.shape[2] and coords.shape[1] == 3
+        out = residual = gate = None
         if not self.training and not torch.is_grad_enabled() and self.resolution in FUSED_RESOLUTIONS:
             pf = self.point_features.layers
             if len(pf) == 3 and features.is_cuda:  # one conv -> norm -> Swish: joined to the voxel branch in one pass
-                from . import fused as F_
+                from . import fused
 
                 feats = features.contiguous()
-                h, st = F_.pw_conv(feats, pf[0])
-                data.features = self._voxel_branch_fused(feats, coords, cond, point=(h, st, norm_fin(pf[1], feats.shape[2], cond)),
-                                                         geo=data.geo)
-                if self.attn is not None:
-                    data.features = self.attn(data.features)
-                return data
-            fused = self._voxel_branch_fused(features, coords, cond, geo=data.geo)
+                h, st = fused.pw_conv(feats, pf[0])
+                out = self._voxel_branch_fused(feats, coords, cond, point=(h, st, norm_fin(pf[1], feats.shape[2], cond)), geo=data.geo)
+            else:  # (a longer point branch; __init__ builds none)
+                residual = self._voxel_branch_fused(features, coords, cond, geo=data.geo)
         else:
             from . import dense
 
@@ -651,18 +624,14 @@ class PVConv(nn.Module):
                 # (no grid-sized mean / div / add), the gate and the sum with the point branch into the point branch's last norm
                 v, vmean = dense.conv_norm_act(v, vl[4], vl[5], cond, swish=False, want_mean=True)
                 gate = dense.se_gate(vmean, vl[6].fc)
-                dv = L.trilinear_devoxelize(v, vcoords, self.resolution, self.training)
-                data.features = self.point_features.run(features, cond, residual=dv, rgate=gate)
-                if self.attn is not None:  # models/pvcnn.py:327-328
-                    data.features = self.attn(data.features)
-                return data
-            v = dense.conv_norm_act(v, vl[4], vl[5], cond, swish=False)
-            if len(vl) > 6:
-                v = vl[6](v)
-            fused = L.trilinear_devoxelize(v, vcoords, self.resolution, self.training)
-        data.features = self.point_features.run(features, cond, residual=fused)
-        if self.attn is not None:  # models/pvcnn.py:327-328
-            data.features = self.attn(data.features)
+            else:
+                v = dense.conv_norm_act(v, vl[4], vl[5], cond, swish=False)
+                if len(vl) > 6:
+                    v = vl[6](v)
+            residual = L.trilinear_devoxelize(v, vcoords, self.resolution, self.training)
+        if out is None:
+            out = self.point_features.run(features, cond, residual=residual, rgate=gate)
+        data.features = out if self.attn is None else self.attn(out)  # models/pvcnn.py:327-328
         return data
 
 
@@ -672,15 +641,50 @@ FUSED_RESOLUTIONS = (4, 8, 16, 32)  # the fused inference branch's grids; any ot
 def compact_plan():
     """resolutions whose first / second PVConv convolution run in compact (voxel-level sparse) form;
     default: r = 16 (measured: +2.5 %; at r = 32 the brick-level lists win, at r = 8 the dense kernel); P2PB_EXPERIMENT="compact=32,16:16" overrides, empty = off"""
-    import os
-
     from . import fused
 
     if fused.conv_math() not in fused.SPLIT_MATHS:  # the compact kernel exists in the split-operand arithmetic only
         return set(), set()
-    spec = _experiment.get("compact", "16:16")
-    parts = (spec.split(":") + [""])[:2]
-    return tuple({int(t) for t in p.split(",") if t.strip()} for p in parts)
+    return _experiment.resolution_pair("compact", "16:16")
+
+
+def voxel_conv_plan(r, sparse_conv=True):
+    """-> (form of the first convolution, form of the second one, kind of lists they read) of a PVConv at resolution r whose
+    `sparse_conv` flag is given: the ONE rule that Geometry (which lists to prepare) and PVConv._voxel_branch_fused (which
+    kernels to run) both ask. Forms: "compact" (voxel-level sparsity: only the outputs within one (first conv) / two (second
+    conv) voxels of an occupied voxel are computed, packed densely into the MFMA column tiles; fused.active_lists), "bricks"
+    (the active 4x8x8 bricks; fused.brick_lists), "dense". Kinds: "active", "bricks", None. All forms compute the same function;
+    a second convolution that is not dense runs in far-field form"""
+    if not sparse_conv:
+        return "dense", "dense", None
+    c1, c2 = compact_plan()
+    if r in c1 or r in c2:
+        return "compact" if r in c1 else "dense", "compact" if r in c2 else "dense", "active"
+    if r >= 32:  # at r = 16 every 4x8x8 brick touches the surface: dense is faster
+        return "bricks", "bricks", "bricks"
+    return "dense", "dense", None
+
+
+def _voxel_lists(kind, cnt, r):
+    from . import fused
+
+    return (fused.active_lists if kind == "active" else fused.brick_lists)(cnt, r)
+
+
+def _voxel_conv(form, x, conv, lists, counts, which, in_scale=None, in_shift=None, swish=False, in_sub=None, out_class=None, pre=False,
+                unread_unwritten=False):
+    """one convolution of a PVConv on voxel-major grids in the form voxel_conv_plan chose; which = 0: the first one, 1: the
+    second. unread_unwritten: the caller reads y only where the sparse form computes it, so the constants outside that set stay
+    unwritten (compact: listed_only, bricks: active_only; the statistics stay exact); the dense form writes everything"""
+    from . import fused
+
+    if form == "compact":
+        return fused.conv3d_k3_compact(x, conv, lists, counts, which, in_scale, in_shift, swish, in_sub=in_sub, out_class=out_class,
+                                       pre=pre, listed_only=unread_unwritten)
+    if form == "bricks":
+        return fused.conv3d_k3_sparse(x, conv, lists, counts, which, in_scale, in_shift, swish, in_sub=in_sub, out_class=out_class,
+                                      channels_last=True, pre=pre, active_only=unread_unwritten)
+    return fused.conv3d_k3(x, conv, in_scale, in_shift, swish=swish, compact=True, channels_last=True, pre=pre)
 
 
 class BallQuery(nn.Module):
@@ -996,15 +1000,11 @@ class Geometry:
                     continue
                 vcoords, vox = L.voxel_coords(c, r, normalize, eps)
                 cnt, ws = fused.voxel_sort(vox, r)
-                lists = counts = None
-                c1, c2 = compact_plan()
-                if r in c1 or r in c2:
-                    lists, counts = fused.active_lists(cnt, r)
-                elif r == 32:  # (the brick-list sparse convolutions: _voxel_branch_fused)
-                    lists, counts = fused.brick_lists(cnt, r)
+                kind = voxel_conv_plan(r)[2]  # (no block at hand: what one with sparse_conv on reads)
+                lists, counts = _voxel_lists(kind, cnt, r) if kind is not None else (None, None)
                 ev = torch.cuda.Event()
                 ev.record(stream)
-                self.voxel[(i, r)] = (vcoords, cnt, ws, lists, counts, ev)
+                self.voxel[(i, r)] = (vcoords, cnt, ws, kind, lists, counts, ev)
 
         # Level 0's voxel preparation runs on the MAIN stream, behind the fork (round 5, tools/exp_stamps.py): in front of the
         # level-0 farthest-point sampling on the side stream it delayed that 1.7 ms dependent chain by its own 0.25 ms, and once the
@@ -1050,7 +1050,7 @@ class Geometry:
         *vals, ev = item
         self.main.wait_event(ev)
         for v in vals:
-            if v is not None:
+            if torch.is_tensor(v):
                 v.record_stream(self.main)
         return vals
 
