@@ -725,6 +725,38 @@ int p2pb_merge_accumulate(int npatch, int k, const float *pred, const int *idx, 
                           int *counts, void *stream);
 int p2pb_merge_finish(int n, const double *sums, const int *counts, const float *original, float *out, void *stream);
 
+/* ---- room pipeline, batched patch construction (denoise_room.py create_patches_batched; csrc/room_patches.hip) -------
+ * create_patches (denoise_room.py:352-421) for the whole room in a constant number of launches, same bits as the loop
+ * of batch-1 FPS calls. points f32[n,3] (point-major), idx_flat i32[idx_len] and offsets i64[s+1] are the radius lists.
+ *
+ * p2pb_room_fps_jobs: `jobs` independent FPS jobs, one workgroup each. table i64[jobs,5], one row per job =
+ * (list offset into idx_flat, list length L, start position in [0, L), output row in [0, rows), workspace offset in
+ * floats). The job's cloud is points[idx_flat[off .. off+L)]; the result is exactly furthest point sampling of m samples
+ * on that cloud with positions 0 and `start` swapped, picks mapped back (first pick = start; running minimum 1e38f;
+ * fma(dz,dz,fma(dy,dy,dx*dx)); ties in the order of the reference's 512-thread block over the swapped positions).
+ * picks i32[rows,m] receives POSITIONS WITHIN THE LIST (0 .. L-1), not room indices; rows no job names stay untouched.
+ * All jobs of one call belong to one tier: tier t takes L <= p2pb_room_fps_tier_capacity(t), t = 0..3 keep the list in
+ * registers (1024, 4096, 8192, 16384), t = 4 takes any longer list: the job gathers it once into (x, y, z, running minimum)
+ * records in ws and streams those every round (ws f32[ws_floats], 16-byte aligned, p2pb_room_fps_jobs_ws_bytes(sum of
+ * the streamed jobs' L) bytes; every streamed job owns 4 L floats at its workspace offset, a multiple of 4; ws may be NULL
+ * for t < 4). A row that breaks any of these bounds, or a list entry outside [0, n), is passed
+ * over on the device: nothing is read or written out of bounds.
+ * p2pb_room_list_bounds: bounds f32[s,6] = (min x, y, z, max x, y, z) over each list's points, exact fp32.
+ * p2pb_room_assemble_patches: xyz f32[npatch,k,3] and idx i64[npatch,k] (room indices) of both kinds of patch.
+ * table i64[npatch,4], one row per patch = (list offset, list length L, source, kind). kind 1: an FPS patch, source =
+ * its row of picks i32[rows,k]. kind 0: a padded patch (L < k): the L list points in order, then entry L+q = the list
+ * position pad_r[source+q] (i64[pad_total]) moved by jitter[source+q] (f32[pad_total,3]), one fp32 add per coordinate.
+ * Every launch goes on `stream`. -> 0, P2PB_EINVAL or a hipError_t code */
+int p2pb_room_fps_tier_capacity(int tier);
+size_t p2pb_room_fps_jobs_ws_bytes(long long stream_points);
+int p2pb_room_fps_jobs(int tier, int jobs, int m, int n, const float *points, const int *idx_flat, long long idx_len,
+                       const long long *table, int rows, float *ws, long long ws_floats, int *picks, void *stream);
+int p2pb_room_list_bounds(int s, int n, const float *points, const int *idx_flat, long long idx_len,
+                          const long long *offsets, float *bounds, void *stream);
+int p2pb_room_assemble_patches(int npatch, int k, int n, const float *points, const int *idx_flat, long long idx_len,
+                               const long long *table, const int *picks, int rows, const long long *pad_r,
+                               const float *jitter, long long pad_total, float *xyz, long long *idx, void *stream);
+
 /* ---- packs of the ADJOINT (data-gradient) operator, read straight from the forward layer's weight ----
  * dX of a layer is the same convolution kernel on dY with the transposed weight (and the taps point-reflected for the
  * 3x3x3 convolution). These pack variants take the FORWARD weight -- w_forward f32[cin][cout][27] resp. f32[cin][cout],

@@ -55,6 +55,9 @@ SYMBOLS = [
     "p2pb_vit_layernorm", "p2pb_vit_linear", "p2pb_vit_patch_embed_ws_floats", "p2pb_vit_patch_embed",
     "p2pb_vit_attention_forward", "p2pb_imgfeat_sample_grid", "p2pb_imgfeat_fuse_grid",
     "p2pb_vit_layernorm_f16", "p2pb_vit_linear_f16", "p2pb_vit_attention_forward_f16",
+    # room pipeline, batched patch construction
+    "p2pb_room_fps_tier_capacity", "p2pb_room_fps_jobs_ws_bytes", "p2pb_room_fps_jobs", "p2pb_room_list_bounds",
+    "p2pb_room_assemble_patches",
 ]
 
 ABI_VERSION = 13  # include/p2pb_hip.h P2PB_ABI_VERSION this binding was written against (tests/test_abi.py compares the two)
@@ -99,6 +102,7 @@ def lib():
         _lib.p2pb_occupancy_ws_bytes.restype = ctypes.c_size_t
         _lib.p2pb_imgfeat_visibility_ws_bytes.restype = ctypes.c_size_t
         _lib.p2pb_vit_patch_embed_ws_floats.restype = ctypes.c_size_t
+        _lib.p2pb_room_fps_jobs_ws_bytes.restype = ctypes.c_size_t
         have = _lib.p2pb_version() if hasattr(_lib, "p2pb_version") else None
         if have != ABI_VERSION:
             bad, _lib = _lib, None

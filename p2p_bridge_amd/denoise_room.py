@@ -7,6 +7,7 @@ sklearn KD-tree, numba and fpsample:
     centres     third_party/pvcnn furthest_point_sample over the whole room            csrc/sampling.hip (pruned large-cloud FPS)
     patches     KDTree.query_radius(centres, r = 0.3 | 0.5)                            csrc/room.hip radius_count / fill
     resample    small patches: random duplicates + 1 % jitter; large: FPS subsets      host RNG draws + csrc/sampling.hip
+                  batched_patches=True: the same patches, all of the room's at once    host RNG draws + csrc/room_patches.hip
     sampler     per-patch centre and scale (NOT the object pipeline's global scale)    P2PB.sample (hipGraph replay)
     merge       numba running mean over the overlapping patches                        csrc/room.hip merge_*
 
@@ -17,6 +18,11 @@ fpsample's bucket FPS (its start point is random and comes from its own Rust RNG
 /root/reference and not installable here: the contract restated for them -- every random draw from ONE caller-supplied torch CPU
 generator in a fixed order, exact FPS from a drawn start index -- is "parity unpinned" against the reference and pinned to the test
 oracle's restatement of the same contract.
+
+Two builders cut the patches, with the same bits: `create_patches` walks the centres and issues one batch-1 FPS launch per subset;
+`create_patches_batched` takes every random draw on the host first (`plan_patches`), then runs all FPS subsets of the room as ragged
+jobs, one workgroup each, in one launch per size tier (`fps_jobs`), one bounding-box launch and one assembly launch. denoise_room
+takes the second with batched_patches=True and then gathers colours and features per sampler batch instead of for the whole room.
 """
 import ctypes
 from typing import Optional
@@ -24,7 +30,7 @@ from typing import Optional
 import torch
 
 from . import pointnet2_batch_cuda as _ext
-from ._lib import call, check, ptr, stream_ptr
+from ._lib import call, check, lib, ptr, stream_ptr
 
 F32, I32 = torch.float32, torch.int32
 _i = ctypes.c_int
@@ -94,6 +100,128 @@ def create_patches(points, idx_flat, offsets, patch_size, generator, colors=None
                 rgb=torch.stack(rgb) if rgb else None, feats=torch.stack(ft) if ft else None)
 
 
+# ---- the same patches in a constant number of launches (csrc/room_patches.hip) ------------------------------------------------
+FPS_JOB_TIERS = (1024, 4096, 8192, 16384)  # longest list of each register tier of p2pb_room_fps_jobs; longer lists stream
+# library calls of one create_patches_batched: one FPS launch per tier (+ the streaming form), the bounds, the assembly
+BATCHED_MAX_LIBRARY_CALLS = len(FPS_JOB_TIERS) + 1 + 2
+_ll = ctypes.c_longlong
+
+
+def plan_patches(offsets, patch_size, generator):
+    """Host only: every random draw of create_patches, in its order and with its calls, without touching a point.
+    offsets i64[S+1] -> the job tables of the room (P patches in create_patches' order, J FPS subsets, Q padded patches):
+        centre i64[P], kind i64[P] (1 = FPS subset, 0 = padded), cuts i64[P]
+        job_patch i64[J], job_start i64[J]          the patch each FPS job fills and its drawn start position in the list
+        pad_patch i64[Q], pad_ptr i64[Q+1]          the padded patches and their ranges in pad_r / pad_normals
+        pad_r i64[T], pad_normals f32[T,3]          the duplicate draws and the unit normals of the jitter
+    Empty lists are skipped; afterwards `generator` is in the state create_patches leaves it in."""
+    off = offsets.cpu().tolist()
+    centre, kind, cuts, job_patch, job_start, pad_patch, pad_ptr, pad_r, pad_normals = [], [], [], [], [], [], [0], [], []
+    for c in range(len(off) - 1):
+        L = off[c + 1] - off[c]
+        if L <= 0:
+            continue
+        if L < patch_size:
+            diff = patch_size - L
+            pad_r.append(torch.randint(0, L, (diff,), generator=generator))
+            pad_normals.append(torch.randn(diff, 3, generator=generator))
+            pad_patch.append(len(centre))
+            pad_ptr.append(pad_ptr[-1] + diff)
+            centre.append(c), kind.append(0), cuts.append(L)
+        else:
+            for _ in range(L // patch_size + 1):
+                job_start.append(int(torch.randint(0, L, (1,), generator=generator)))
+                job_patch.append(len(centre))
+                centre.append(c), kind.append(1), cuts.append(patch_size)
+    i64 = lambda v: torch.tensor(v, dtype=torch.int64)  # noqa: E731
+    return dict(centre=i64(centre), kind=i64(kind), cuts=i64(cuts), job_patch=i64(job_patch), job_start=i64(job_start),
+                pad_patch=i64(pad_patch), pad_ptr=i64(pad_ptr),
+                pad_r=torch.cat(pad_r) if pad_r else torch.zeros(0, dtype=torch.int64),
+                pad_normals=torch.cat(pad_normals) if pad_normals else torch.zeros(0, 3))
+
+
+def fps_jobs(points, idx_flat, job_off, job_len, job_start, m):
+    """Ragged FPS jobs, one workgroup each (p2pb_room_fps_jobs): job j samples `m` points of the cloud
+    points[idx_flat[job_off[j] : job_off[j] + job_len[j]]] starting at list position job_start[j], with the result of
+    `_fps_from` on that cloud. points f32[N,3], idx_flat i32[total] on the device; job_* host integers [J].
+    -> i32[J,m] on the device: POSITIONS WITHIN THE LIST (list[pick] is the room index). One launch per tier in use."""
+    check(points, F32, "points"), check(idx_flat, I32, "idx_flat")
+    table = torch.stack([torch.as_tensor(v, dtype=torch.int64).cpu().reshape(-1) for v in (job_off, job_len, job_start)], 1)
+    J, total = table.shape[0], idx_flat.numel()
+    if m <= 0:
+        raise ValueError("fps_jobs: m must be positive")
+    picks = torch.empty(J, m, dtype=I32, device=points.device)
+    if J == 0:
+        return picks
+    o, L, st = table.t().contiguous()
+    if bool(((o < 0) | (L < 1) | (o + L > total) | (st < 0) | (st >= L)).any()):
+        raise ValueError("fps_jobs: a job's list lies outside idx_flat, is empty, or its start lies outside the list")
+    tier = torch.bucketize(L, torch.tensor(FPS_JOB_TIERS, dtype=torch.int64))  # edges inclusive: L <= FPS_JOB_TIERS[t]
+    order = torch.argsort(tier, stable=True)
+    streamed = tier == len(FPS_JOB_TIERS)
+    own = torch.where(streamed, 4 * L, torch.zeros_like(L))  # floats of workspace a streamed job owns: (x, y, z, minimum) per point
+    ws_off = torch.cumsum(own, 0) - own
+    rows = torch.cat([table, torch.arange(J)[:, None], ws_off[:, None]], 1)[order].contiguous().to(points.device)
+    ws, ws_floats = None, 0
+    if bool(streamed.any()):
+        ws_floats = int(lib().p2pb_room_fps_jobs_ws_bytes(_ll(int(L[streamed].sum())))) // 4
+        ws = torch.empty(ws_floats, dtype=F32, device=points.device)
+    counts = torch.bincount(tier, minlength=len(FPS_JOB_TIERS) + 1).tolist()
+    lo = 0
+    for t, cnt in enumerate(counts):
+        if cnt > 0:
+            call("p2pb_room_fps_jobs", _i(t), _i(cnt), _i(m), _i(points.shape[0]), ptr(points), ptr(idx_flat), _ll(total),
+                 ptr(rows[lo:lo + cnt]), _i(J), ptr(ws), _ll(ws_floats), ptr(picks), stream_ptr())
+        lo += cnt
+    return picks
+
+
+def create_patches_batched(points, idx_flat, offsets, patch_size, generator, colors=None, feats=None, gather=True):
+    """create_patches with the same result bit for bit (xyz, idx, cuts, rgb, feats) and the same generator state afterwards,
+    in at most BATCHED_MAX_LIBRARY_CALLS library calls and a constant number of torch launches whatever the number of
+    centres: two downloads (offsets, the lists' bounding boxes), nothing per patch that launches or synchronises.
+    gather=False leaves rgb / feats None (denoise_room gathers them per sampler batch: colors[idx[lo:hi]])."""
+    check(points, F32, "points"), check(idx_flat, I32, "idx_flat")
+    dev, n, k = points.device, points.shape[0], patch_size
+    off = offsets.cpu()
+    plan = plan_patches(off, k, generator)
+    c = plan["centre"]
+    P = c.numel()
+    if P == 0:
+        raise RuntimeError("create_patches_batched: no patch (every radius list is empty)")
+    p_off, p_len = off[c], off[c + 1] - off[c]
+    jp = plan["job_patch"]
+    J = jp.numel()
+    picks = fps_jobs(points, idx_flat, p_off[jp], p_len[jp], plan["job_start"], k) if J > 0 else None
+    src = torch.zeros(P, dtype=torch.int64)
+    src[jp] = torch.arange(J)
+    pp = plan["pad_patch"]
+    src[pp] = plan["pad_ptr"][:-1]
+    pad_r = jitter = None
+    T = plan["pad_r"].numel()
+    if T > 0:
+        s = off.numel() - 1
+        bounds = torch.empty(s, 6, dtype=F32, device=dev)
+        offsets_dev = offsets.to(dev, torch.int64).contiguous()
+        call("p2pb_room_list_bounds", _i(s), _i(n), ptr(points), ptr(idx_flat), _ll(idx_flat.numel()), ptr(offsets_dev),
+             ptr(bounds), stream_ptr())
+        b = bounds.cpu()
+        jit = []
+        for q, cq in enumerate(c[pp].tolist()):  # the loop's expressions (level in float64, the product on the host), per padded patch
+            level = float((b[cq, 3:] - b[cq, :3]).double().norm().item()) * 1e-2
+            jit.append(level * plan["pad_normals"][plan["pad_ptr"][q]:plan["pad_ptr"][q + 1]])
+        jitter = torch.cat(jit).contiguous().to(dev)
+        pad_r = plan["pad_r"].to(dev)
+    table = torch.stack([p_off, p_len, src, plan["kind"]], 1).contiguous().to(dev)
+    xyz = torch.empty(P, k, 3, dtype=F32, device=dev)
+    idx = torch.empty(P, k, dtype=torch.int64, device=dev)
+    call("p2pb_room_assemble_patches", _i(P), _i(k), _i(n), ptr(points), ptr(idx_flat), _ll(idx_flat.numel()), ptr(table),
+         ptr(picks), _i(J), ptr(pad_r), ptr(jitter), _ll(T), ptr(xyz), ptr(idx), stream_ptr())
+    return dict(xyz=xyz, idx=idx, cuts=plan["cuts"],
+                rgb=colors[idx] if gather and colors is not None else None,
+                feats=feats[idx] if gather and feats is not None else None)
+
+
 @torch.no_grad()
 def denoise_patch_batch(model, patch_xyz, patch_rgb=None, patch_feats=None, steps=None, use_ema=False,
                         return_steps=False, use_rgb_features=False, point_features=None, graph=False):
@@ -146,11 +274,14 @@ class RunningMean:
 @torch.no_grad()
 def denoise_room(model, room_points, patch_size, k=3, radius=0.5, batch_size=32, steps=None, use_ema=False,
                  colors=None, feats=None, use_rgb_features=False, point_features=None, average_predictions=True,
-                 generator: Optional[torch.Generator] = None, reference_batching=False, graph=False, trace=None):
+                 generator: Optional[torch.Generator] = None, reference_batching=False, graph=False, trace=None,
+                 batched_patches=False):
     """denoise_room.py:main. room_points f32[N,3] on the device -> denoised f32[N,3].
     k: patches per `patch_size` points (args.k); radius: 0.3 for ScanNet++, 0.5 otherwise (:463).
     reference_batching=True reproduces the reference's batch slicing `[start:end]` with end = the batch's LAST index
-    (:498-500), which silently drops the last patch of every batch; the default feeds every patch."""
+    (:498-500), which silently drops the last patch of every batch; the default feeds every patch.
+    batched_patches=True cuts the patches with create_patches_batched (same patches, a constant number of launches) and
+    gathers colours and features per sampler batch: the room's [P, k, C] feature tensor is never materialised."""
     check(room_points, F32, "room_points")
     generator = generator or torch.Generator().manual_seed(42)
     n = room_points.shape[0]
@@ -158,7 +289,10 @@ def denoise_room(model, room_points, patch_size, k=3, radius=0.5, batch_size=32,
     cidx = _ext.furthest_point_sampling_forward(room_points.t().contiguous()[None], n_centres)[0].long()
     centres = room_points[cidx].contiguous()
     idx_flat, offsets = radius_query(centres, room_points, radius)
-    pt = create_patches(room_points, idx_flat, offsets, patch_size, generator, colors, feats)
+    if batched_patches:
+        pt = create_patches_batched(room_points, idx_flat, offsets, patch_size, generator, gather=False)
+    else:
+        pt = create_patches(room_points, idx_flat, offsets, patch_size, generator, colors, feats)
     P = pt["xyz"].shape[0]
     nb = -(-P // batch_size)
     bounds = [(int(c[0]), int(c[-1]) + (0 if reference_batching else 1)) for c in torch.arange(P).tensor_split(nb)]
@@ -167,8 +301,12 @@ def denoise_room(model, room_points, patch_size, k=3, radius=0.5, batch_size=32,
     for lo, hi in bounds:
         if hi <= lo:
             continue
-        rgb = pt["rgb"][lo:hi] if pt["rgb"] is not None else None
-        ft = pt["feats"][lo:hi] if pt["feats"] is not None else None
+        if batched_patches:
+            rgb = colors[pt["idx"][lo:hi]] if colors is not None else None
+            ft = feats[pt["idx"][lo:hi]] if feats is not None else None
+        else:
+            rgb = pt["rgb"][lo:hi] if pt["rgb"] is not None else None
+            ft = pt["feats"][lo:hi] if pt["feats"] is not None else None
         den, _ = denoise_patch_batch(model, pt["xyz"][lo:hi], rgb, ft, steps, use_ema, False, use_rgb_features,
                                      point_features, graph)
         if merge is not None:
