@@ -39,7 +39,9 @@ extern "C" {
  * p2pb_conv3d_k3_forward_sparse, arithmetic code 3 in p2pb_set_split_terms_thread, p2pb_group_sub_stats*, p2pb_se_gate_*,
  * p2pb_conv3d_k3_wgrad_occ*, the *_amax / *_adjoint packs).
  * A binding must compare p2pb_version() with the P2PB_ABI_VERSION it was written against and refuse a mismatch
- * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently. */
+ * (p2p_bridge_amd/_lib.py does): a stale library behind P2PB_LIB_PATH otherwise fails late, or silently differently.
+ * The Python binding takes every entry point's name, return type and parameter types, and this version, from this file
+ * when it loads, so a declaration must keep the plain `type name(params);` form (no macros, no function pointers). */
 #define P2PB_ABI_VERSION 13
 
 /* library / device info --------------------------------------------------------------------- */

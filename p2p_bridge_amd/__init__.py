@@ -25,11 +25,11 @@ class deterministic:
     def __init__(self, on: bool = True):
         import torch
 
-        from ._lib import lib
+        from ._lib import ask
 
-        self.prev = (bool(lib().p2pb_get_deterministic()), torch.are_deterministic_algorithms_enabled(),
+        self.prev = (bool(ask("p2pb_get_deterministic")), torch.are_deterministic_algorithms_enabled(),
                      torch.is_deterministic_algorithms_warn_only_enabled())
-        lib().p2pb_set_deterministic(int(on))
+        ask("p2pb_set_deterministic", int(on))
         torch.use_deterministic_algorithms(bool(on), warn_only=True)
 
     def __enter__(self):
@@ -38,9 +38,9 @@ class deterministic:
     def __exit__(self, *exc):
         import torch
 
-        from ._lib import lib
+        from ._lib import ask
 
-        lib().p2pb_set_deterministic(int(self.prev[0]))
+        ask("p2pb_set_deterministic", int(self.prev[0]))
         torch.use_deterministic_algorithms(self.prev[1], warn_only=self.prev[2])
         return False
 

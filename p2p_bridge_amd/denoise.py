@@ -15,8 +15,7 @@ from collections import namedtuple
 import torch
 
 from . import pointnet2_batch_cuda as _ext
-from ._lib import call, check, lib, ptr, stream_ptr
-import ctypes
+from ._lib import ask, call, check, ptr, stream_ptr
 
 F32, I32 = torch.float32, torch.int32
 _KNN = namedtuple("KNN", "dists idx knn")  # field names of pytorch3d.ops.knn._KNN
@@ -37,10 +36,9 @@ def knn_points(p1, p2, K=1, return_nn=False):
     dists = torch.empty(b, s, k, dtype=F32, device=dev)
     idx = torch.empty(b, s, k, dtype=I32, device=dev)
     nn = torch.empty(b, s, k, 3, dtype=F32, device=dev) if return_nn else None
-    ws = torch.empty(int(lib().p2pb_knn_points_ws_bytes(ctypes.c_int(b), ctypes.c_int(s), ctypes.c_int(n))),
+    ws = torch.empty(int(ask("p2pb_knn_points_ws_bytes", b, s, n)),
                      dtype=torch.uint8, device=dev)
-    call("p2pb_knn_points", ctypes.c_int(b), ctypes.c_int(s), ctypes.c_int(n), ctypes.c_int(k), ptr(p1), ptr(p2),
-         ptr(dists), ptr(idx), ptr(nn), ptr(ws), stream_ptr())
+    call("p2pb_knn_points", b, s, n, k, ptr(p1), ptr(p2), ptr(dists), ptr(idx), ptr(nn), ptr(ws), stream_ptr())
     return _KNN(dists, idx.long(), nn)
 
 

@@ -24,16 +24,14 @@ Two builders cut the patches, with the same bits: `create_patches` walks the cen
 jobs, one workgroup each, in one launch per size tier (`fps_jobs`), one bounding-box launch and one assembly launch. denoise_room
 takes the second with batched_patches=True and then gathers colours and features per sampler batch instead of for the whole room.
 """
-import ctypes
 from typing import Optional
 
 import torch
 
 from . import pointnet2_batch_cuda as _ext
-from ._lib import call, check, lib, ptr, stream_ptr
+from ._lib import ask, call, check, lib, ptr, stream_ptr  # noqa: F401  (lib: tests reach the loaded library through this module)
 
 F32, I32 = torch.float32, torch.int32
-_i = ctypes.c_int
 
 
 def radius_query(centers, points, radius):
@@ -41,13 +39,12 @@ def radius_query(centers, points, radius):
     check(centers, F32, "centers"), check(points, F32, "points")
     s, n = centers.shape[0], points.shape[0]
     counts = torch.empty(s, dtype=I32, device=points.device)
-    call("p2pb_radius_count", _i(s), _i(n), ptr(centers), ptr(points), ctypes.c_float(radius), ptr(counts), stream_ptr())
+    call("p2pb_radius_count", s, n, ptr(centers), ptr(points), radius, ptr(counts), stream_ptr())
     offsets = torch.zeros(s + 1, dtype=torch.int64, device=points.device)
     offsets[1:] = torch.cumsum(counts.long(), 0)
     total = int(offsets[-1].item())  # (ragged lists: the sizes are needed on the host anyway)
     out = torch.empty(max(total, 1), dtype=I32, device=points.device)
-    call("p2pb_radius_fill", _i(s), _i(n), ptr(centers), ptr(points), ctypes.c_float(radius), ptr(offsets), ptr(out),
-         stream_ptr())
+    call("p2pb_radius_fill", s, n, ptr(centers), ptr(points), radius, ptr(offsets), ptr(out), stream_ptr())
     return out[:total], offsets
 
 
@@ -104,7 +101,6 @@ def create_patches(points, idx_flat, offsets, patch_size, generator, colors=None
 FPS_JOB_TIERS = (1024, 4096, 8192, 16384)  # longest list of each register tier of p2pb_room_fps_jobs; longer lists stream
 # library calls of one create_patches_batched: one FPS launch per tier (+ the streaming form), the bounds, the assembly
 BATCHED_MAX_LIBRARY_CALLS = len(FPS_JOB_TIERS) + 1 + 2
-_ll = ctypes.c_longlong
 
 
 def plan_patches(offsets, patch_size, generator):
@@ -164,14 +160,14 @@ def fps_jobs(points, idx_flat, job_off, job_len, job_start, m):
     rows = torch.cat([table, torch.arange(J)[:, None], ws_off[:, None]], 1)[order].contiguous().to(points.device)
     ws, ws_floats = None, 0
     if bool(streamed.any()):
-        ws_floats = int(lib().p2pb_room_fps_jobs_ws_bytes(_ll(int(L[streamed].sum())))) // 4
+        ws_floats = int(ask("p2pb_room_fps_jobs_ws_bytes", int(L[streamed].sum()))) // 4
         ws = torch.empty(ws_floats, dtype=F32, device=points.device)
     counts = torch.bincount(tier, minlength=len(FPS_JOB_TIERS) + 1).tolist()
     lo = 0
     for t, cnt in enumerate(counts):
         if cnt > 0:
-            call("p2pb_room_fps_jobs", _i(t), _i(cnt), _i(m), _i(points.shape[0]), ptr(points), ptr(idx_flat), _ll(total),
-                 ptr(rows[lo:lo + cnt]), _i(J), ptr(ws), _ll(ws_floats), ptr(picks), stream_ptr())
+            call("p2pb_room_fps_jobs", t, cnt, m, points.shape[0], ptr(points), ptr(idx_flat), total,
+                 ptr(rows[lo:lo + cnt]), J, ptr(ws), ws_floats, ptr(picks), stream_ptr())
         lo += cnt
     return picks
 
@@ -203,7 +199,7 @@ def create_patches_batched(points, idx_flat, offsets, patch_size, generator, col
         s = off.numel() - 1
         bounds = torch.empty(s, 6, dtype=F32, device=dev)
         offsets_dev = offsets.to(dev, torch.int64).contiguous()
-        call("p2pb_room_list_bounds", _i(s), _i(n), ptr(points), ptr(idx_flat), _ll(idx_flat.numel()), ptr(offsets_dev),
+        call("p2pb_room_list_bounds", s, n, ptr(points), ptr(idx_flat), idx_flat.numel(), ptr(offsets_dev),
              ptr(bounds), stream_ptr())
         b = bounds.cpu()
         jit = []
@@ -215,8 +211,8 @@ def create_patches_batched(points, idx_flat, offsets, patch_size, generator, col
     table = torch.stack([p_off, p_len, src, plan["kind"]], 1).contiguous().to(dev)
     xyz = torch.empty(P, k, 3, dtype=F32, device=dev)
     idx = torch.empty(P, k, dtype=torch.int64, device=dev)
-    call("p2pb_room_assemble_patches", _i(P), _i(k), _i(n), ptr(points), ptr(idx_flat), _ll(idx_flat.numel()), ptr(table),
-         ptr(picks), _i(J), ptr(pad_r), ptr(jitter), _ll(T), ptr(xyz), ptr(idx), stream_ptr())
+    call("p2pb_room_assemble_patches", P, k, n, ptr(points), ptr(idx_flat), idx_flat.numel(), ptr(table),
+         ptr(picks), J, ptr(pad_r), ptr(jitter), T, ptr(xyz), ptr(idx), stream_ptr())
     return dict(xyz=xyz, idx=idx, cuts=plan["cuts"],
                 rgb=colors[idx] if gather and colors is not None else None,
                 feats=feats[idx] if gather and feats is not None else None)
@@ -261,12 +257,12 @@ class RunningMean:
         pred = pred.contiguous().float()
         idx32 = idx.int().contiguous()  # (named: a temporary would be freed -- and its block reused -- before the launch)
         cuts32 = cuts.to(pred.device).int().contiguous()
-        call("p2pb_merge_accumulate", _i(pred.shape[0]), _i(pred.shape[1]), ptr(pred), ptr(idx32), ptr(cuts32),
+        call("p2pb_merge_accumulate", pred.shape[0], pred.shape[1], ptr(pred), ptr(idx32), ptr(cuts32),
              ptr(self.sums), ptr(self.counts), stream_ptr())
 
     def result(self):
         out = torch.empty_like(self.points)
-        call("p2pb_merge_finish", _i(self.points.shape[0]), ptr(self.sums), ptr(self.counts), ptr(self.points), ptr(out),
+        call("p2pb_merge_finish", self.points.shape[0], ptr(self.sums), ptr(self.counts), ptr(self.points), ptr(out),
              stream_ptr())
         return out
 

@@ -13,15 +13,13 @@ left them on torch / MIOpen in training.
 The parameters stay ordinary nn.Conv3d / nn.Conv1d / nn.Conv2d modules (reference checkpoint names); only the
 function applied to them changes. Transformed / packed weights are cached per parameter version.
 """
-import ctypes
 import types
 
 import torch
 
 from . import fused
-from ._lib import call, lib, ptr, stream_ptr
+from ._lib import ask, call, ptr, stream_ptr
 
-_i = ctypes.c_int
 F32 = torch.float32
 SPARSE_WGRAD = True  # weight gradient of a PVConv's first convolution over the occupied voxels only (tests flip it to compare)
 USE_HIP = True  # tools/exp_train_step.py flips this to time the torch / MIOpen dense layers on the same graph
@@ -171,16 +169,15 @@ class _Conv3dK3(torch.autograd.Function):
                 gb = torch.empty(co, dtype=F32, device=x.device) if want_b else None
                 if occ is not None:  # x is zero outside the occupied voxels: K = occupied voxels (csrc/wgrad_occ.hip, exact fp32)
                     cnt, npts = occ
-                    ws = torch.empty(lib().p2pb_conv3d_k3_wgrad_occ_ws_floats(_i(b), _i(ci), _i(co), _i(r), _i(npts)), dtype=F32,
+                    ws = torch.empty(ask("p2pb_conv3d_k3_wgrad_occ_ws_floats", b, ci, co, r, npts), dtype=F32,
                                      device=x.device)
-                    call("p2pb_conv3d_k3_wgrad_occ", _i(b), _i(ci), _i(co), _i(r), _i(npts), ptr(x), ptr(gy), ptr(cnt), ptr(gw),
+                    call("p2pb_conv3d_k3_wgrad_occ", b, ci, co, r, npts, ptr(x), ptr(gy), ptr(cnt), ptr(gw),
                          ptr(gb), ptr(ws), stream_ptr())
                     return gw, gb
-                math = _i(train_math())
-                ws = torch.empty(lib().p2pb_conv3d_k3_wgrad_ws_floats(_i(b), _i(ci), _i(co), _i(r), math), dtype=F32,
+                math = train_math()
+                ws = torch.empty(ask("p2pb_conv3d_k3_wgrad_ws_floats", b, ci, co, r, math), dtype=F32,
                                  device=x.device)
-                call("p2pb_conv3d_k3_wgrad", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(gy), ptr(gw), ptr(gb), ptr(ws),
-                     math, stream_ptr())
+                call("p2pb_conv3d_k3_wgrad", b, ci, co, r, ptr(x), ptr(gy), ptr(gw), ptr(gb), ptr(ws), math, stream_ptr())
                 return gw, gb
 
             gw, gb = _on_wgrad_stream(wgrad, x, gy)
@@ -223,11 +220,10 @@ class _Pointwise(torch.autograd.Function):
             def wgrad():
                 gw = torch.empty(co, ci, dtype=F32, device=x.device)
                 gb = torch.empty(co, dtype=F32, device=x.device) if want_b else None
-                math = _i(train_math())
-                ws = torch.empty(lib().p2pb_pointwise_wgrad_ws_floats(_i(b), _i(ci), _i(co), _i(p), math), dtype=F32,
+                math = train_math()
+                ws = torch.empty(ask("p2pb_pointwise_wgrad_ws_floats", b, ci, co, p, math), dtype=F32,
                                  device=x.device)
-                call("p2pb_pointwise_wgrad", _i(b), _i(ci), _i(co), _i(p), ptr(x), ptr(gy), ptr(gw), ptr(gb), ptr(ws),
-                     math, stream_ptr())
+                call("p2pb_pointwise_wgrad", b, ci, co, p, ptr(x), ptr(gy), ptr(gw), ptr(gb), ptr(ws), math, stream_ptr())
                 return gw.view(conv.weight.shape), gb
 
             gw, gb = _on_wgrad_stream(wgrad, x, gy)
@@ -259,9 +255,8 @@ class _NormAct(torch.autograd.Function):
         shift = torch.empty_like(scale)
         mr = torch.empty(b, groups, 2, dtype=F32, device=x.device)
         chmean = torch.empty(b, c, dtype=F32, device=x.device) if want_mean else None
-        call("p2pb_gn_affine_params_ex", _i(b), _i(c), _i(groups), _i(stats.shape[1]), ctypes.c_double(float(p)),
-             ptr(stats), ptr(gamma), ptr(beta), ptr(style), _i(style.stride(0) if style is not None else 0),
-             ctypes.c_float(eps), ptr(scale), ptr(shift), ptr(chmean), ptr(mr), stream_ptr())
+        call("p2pb_gn_affine_params_ex", b, c, groups, stats.shape[1], float(p), ptr(stats), ptr(gamma), ptr(beta), ptr(style),
+             style.stride(0) if style is not None else 0, eps, ptr(scale), ptr(shift), ptr(chmean), ptr(mr), stream_ptr())
         drop_p, seed, salt = drop if drop is not None else (0.0, None, 0)
         ctx.res_shape = None
         if residual is None and drop is None:
@@ -272,8 +267,8 @@ class _NormAct(torch.autograd.Function):
                 residual = residual.reshape(b, c, p).contiguous()
                 rgate = rgate.reshape(b, c).contiguous() if rgate is not None else None
             y = torch.empty_like(x3)
-            call("p2pb_affine_act_train", _i(b), _i(c), _i(p), ptr(x3), ptr(scale), ptr(shift), _i(int(bool(swish))), ptr(residual),
-                 ptr(rgate), ctypes.c_float(drop_p), ptr(seed), ctypes.c_uint(salt), ptr(y), stream_ptr())
+            call("p2pb_affine_act_train", b, c, p, ptr(x3), ptr(scale), ptr(shift), int(bool(swish)), ptr(residual),
+                 ptr(rgate), drop_p, ptr(seed), salt, ptr(y), stream_ptr())
         ctx.save_for_backward(x3, scale, shift, mr, gamma, beta, style, residual if rgate is not None else None, rgate, seed)
         ctx.groups, ctx.swish, ctx.drop_p, ctx.salt, ctx.has_res = groups, bool(swish), float(drop_p), int(salt), residual is not None
         ctx.x_shape = x.shape
@@ -307,9 +302,9 @@ class _NormAct(torch.autograd.Function):
             dres = gy.contiguous()  # (an ungated residual: its gradient is gy itself)
         if gmean is not None:
             gmean = gmean.contiguous()
-        call("p2pb_norm_act_backward_ex", _i(b), _i(c), _i(groups), _i(p), ptr(x3), ptr(gy), ptr(scale), ptr(shift), ptr(mr),
-             ptr(gamma), ptr(beta), ptr(style), _i(style.stride(0) if style is not None else 0), _i(int(ctx.swish)),
-             ctypes.c_long(pitch), ptr(gmean), ptr(residual), ptr(rgate), ctypes.c_float(ctx.drop_p), ptr(seed), ctypes.c_uint(ctx.salt), ptr(dx),
+        call("p2pb_norm_act_backward_ex", b, c, groups, p, ptr(x3), ptr(gy), ptr(scale), ptr(shift), ptr(mr),
+             ptr(gamma), ptr(beta), ptr(style), style.stride(0) if style is not None else 0, int(ctx.swish),
+             pitch, ptr(gmean), ptr(residual), ptr(rgate), ctx.drop_p, ptr(seed), ctx.salt, ptr(dx),
              ptr(dgamma), ptr(dbeta), ptr(dstyle), ptr(dres if rgate is not None else None), ptr(drgate), ptr(ws), stream_ptr())
         if dres is not None:
             dres = dres.view(ctx.res_shape)
@@ -326,7 +321,7 @@ class _SEGate(torch.autograd.Function):
         mean, w1, w2 = mean.contiguous(), w1.contiguous(), w2.contiguous()
         hid = torch.empty(b, hidden, dtype=F32, device=mean.device)
         gate = torch.empty(b, c, dtype=F32, device=mean.device)
-        call("p2pb_se_gate_forward", _i(b), _i(c), _i(hidden), ptr(mean), ptr(w1), ptr(w2), ptr(hid), ptr(gate), stream_ptr())
+        call("p2pb_se_gate_forward", b, c, hidden, ptr(mean), ptr(w1), ptr(w2), ptr(hid), ptr(gate), stream_ptr())
         ctx.save_for_backward(mean, w1, w2, hid, gate)
         return gate
 
@@ -337,7 +332,7 @@ class _SEGate(torch.autograd.Function):
         hidden = w1.shape[0]
         dmean, dw1, dw2 = torch.empty_like(mean), torch.empty_like(w1), torch.empty_like(w2)
         ws = torch.empty(b * (c + hidden), dtype=F32, device=mean.device)
-        call("p2pb_se_gate_backward", _i(b), _i(c), _i(hidden), ptr(mean), ptr(w1), ptr(w2), ptr(hid), ptr(gate),
+        call("p2pb_se_gate_backward", b, c, hidden, ptr(mean), ptr(w1), ptr(w2), ptr(hid), ptr(gate),
              ptr(dgate.contiguous()), ptr(dmean), ptr(dw1), ptr(dw2), ptr(ws), stream_ptr())
         return dmean, dw1, dw2
 
@@ -353,7 +348,7 @@ class _RowMax(torch.autograd.Function):
         rows = x.numel() // u
         y = torch.empty(x.shape[:-1], dtype=F32, device=x.device)
         idx = torch.empty(x.shape[:-1], dtype=torch.int32, device=x.device)
-        call("p2pb_row_max_forward", ctypes.c_long(rows), _i(u), ptr(x), ptr(y), ptr(idx), stream_ptr())
+        call("p2pb_row_max_forward", rows, u, ptr(x), ptr(y), ptr(idx), stream_ptr())
         ctx.save_for_backward(idx)
         ctx.u = u
         return y
@@ -363,7 +358,7 @@ class _RowMax(torch.autograd.Function):
         (idx,) = ctx.saved_tensors
         gy = gy.contiguous()
         gx = torch.empty(tuple(idx.shape) + (ctx.u,), dtype=F32, device=gy.device)
-        call("p2pb_row_max_backward", ctypes.c_long(idx.numel()), _i(ctx.u), ptr(gy), ptr(idx), ptr(gx), stream_ptr())
+        call("p2pb_row_max_backward", idx.numel(), ctx.u, ptr(gy), ptr(idx), ptr(gx), stream_ptr())
         return gx
 
 

@@ -38,14 +38,13 @@ published code FROM MEMORY and is not pinned by any stored result (INTEGRATION.m
 
 The SwiGLU giant (vitg14) and the register-token variants (*_reg) are not supported and raise ValueError.
 """
-import ctypes
 import math
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ._lib import call, lib, ptr, stream_ptr
+from ._lib import ask, call, ptr, stream_ptr
 
 F16, F32 = torch.float16, torch.float32
 IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)
@@ -79,8 +78,8 @@ def layernorm(x, weight, bias, eps=1e-6, out_dtype=F32):
     if out_dtype not in (F32, F16):
         raise ValueError(f"layernorm: out_dtype {out_dtype} is not float32 or float16")
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    call("p2pb_vit_layernorm" if out_dtype == F32 else "p2pb_vit_layernorm_f16", ctypes.c_int(x.numel() // c), ctypes.c_int(c),
-         ptr(x), ptr(weight), ptr(bias), ctypes.c_float(eps), ptr(y), stream_ptr())
+    call("p2pb_vit_layernorm" if out_dtype == F32 else "p2pb_vit_layernorm_f16", x.numel() // c, c,
+         ptr(x), ptr(weight), ptr(bias), eps, ptr(y), stream_ptr())
     return y
 
 
@@ -99,8 +98,7 @@ def linear(x, weight, bias, gelu=False, residual=None, gamma=None):
             raise ValueError(f"linear: residual {list(residual.shape)}, gamma {list(gamma.shape)}")
     y = residual if residual is not None else torch.empty(m, n, dtype=F32, device=x.device)
     epi = EPI_RESIDUAL if residual is not None else EPI_GELU if gelu else EPI_BIAS
-    call("p2pb_vit_linear", ctypes.c_int(m), ctypes.c_int(n), ctypes.c_int(k), ptr(x), ptr(weight), ptr(bias), ctypes.c_int(epi),
-         ptr(gamma), ptr(y), stream_ptr())
+    call("p2pb_vit_linear", m, n, k, ptr(x), ptr(weight), ptr(bias), epi, ptr(gamma), ptr(y), stream_ptr())
     return y
 
 
@@ -115,8 +113,7 @@ def attention(qkv, heads, n_valid=None):
     if not 1 <= n_valid <= n:
         raise ValueError(f"attention: n_valid {n_valid} outside [1, {n}]")
     out = torch.empty(b, n, heads * HEAD_DIM, dtype=F32, device=qkv.device)
-    call("p2pb_vit_attention_forward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(n), ctypes.c_int(n_valid), ptr(qkv),
-         ptr(out), stream_ptr())
+    call("p2pb_vit_attention_forward", b, heads, n, n_valid, ptr(qkv), ptr(out), stream_ptr())
     return out
 
 
@@ -147,7 +144,7 @@ def linear_half(x, weight, bias, gelu=False, residual=None, gamma=None):
             raise ValueError(f"linear_half: residual {list(residual.shape)}, gamma {list(gamma.shape)}")
     y = residual if residual is not None else torch.empty(m, n, dtype=F16, device=x.device)
     epi = EPI_RESIDUAL if residual is not None else EPI_GELU if gelu else EPI_BIAS
-    call("p2pb_vit_linear_f16", ctypes.c_int(m), ctypes.c_int(n), ctypes.c_int(k), ptr(x), ptr(weight), ptr(bias), ctypes.c_int(epi),
+    call("p2pb_vit_linear_f16", m, n, k, ptr(x), ptr(weight), ptr(bias), epi,
          ptr(gamma), ptr(y), stream_ptr())
     return y
 
@@ -162,7 +159,7 @@ def attention_half(qkv, heads, n_valid=None):
     if not 1 <= n_valid <= n:
         raise ValueError(f"attention_half: n_valid {n_valid} outside [1, {n}]")
     out = torch.empty(b, n, heads * HEAD_DIM, dtype=F16, device=qkv.device)
-    call("p2pb_vit_attention_forward_f16", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(n), ctypes.c_int(n_valid), ptr(qkv),
+    call("p2pb_vit_attention_forward_f16", b, heads, n, n_valid, ptr(qkv),
          ptr(out), stream_ptr())
     return out
 
@@ -397,13 +394,12 @@ class DinoV2(nn.Module):
         rows = b * n
         if hp * wp > 65535 or rows * 4 * c >= 2 ** 31:
             raise ValueError(f"forward_features: {b} images of {hp} x {wp} patches are out of range")
-        ci = ctypes.c_int
         for prm in self.parameters():
             if prm.dtype != F32 or not prm.is_contiguous():
                 raise RuntimeError("DinoV2: parameters must be contiguous float32 (precision='fp16' rounds the matrix "
                                    "operands itself)")
         pos = self.pos_table(hp, wp, dev)
-        ws = torch.empty(int(lib().p2pb_vit_patch_embed_ws_floats(ci(b), ci(hp), ci(wp), ci(ps))), dtype=F32, device=dev)
+        ws = torch.empty(int(ask("p2pb_vit_patch_embed_ws_floats", b, hp, wp, ps)), dtype=F32, device=dev)
         half = self.precision == "fp16"
         act = F16 if half else F32  # the operands of the matrix products: norm outputs, qkv, attention output, hidden
         if half:
@@ -416,18 +412,18 @@ class DinoV2(nn.Module):
         hid = torch.empty(rows, self.blocks[0].mlp.fc1.weight.shape[0], dtype=act, device=dev) if self.depth else None
         s = stream_ptr()
         p = self.patch_embed.proj
-        call("p2pb_vit_patch_embed", ci(b), ci(hp), ci(wp), ci(ps), ci(c), ptr(x), ptr(p.weight), ptr(p.bias),
+        call("p2pb_vit_patch_embed", b, hp, wp, ps, c, ptr(x), ptr(p.weight), ptr(p.bias),
              ptr(self.cls_token), ptr(pos), ptr(ws), ptr(t), s)
 
         def norm(src, ln, dst):
-            call("p2pb_vit_layernorm_f16" if dst.dtype == F16 else "p2pb_vit_layernorm", ci(rows), ci(c), ptr(src),
-                 ptr(ln.weight), ptr(ln.bias), ctypes.c_float(self.eps), ptr(dst), s)
+            call("p2pb_vit_layernorm_f16" if dst.dtype == F16 else "p2pb_vit_layernorm", rows, c, ptr(src),
+                 ptr(ln.weight), ptr(ln.bias), self.eps, ptr(dst), s)
 
         matmul = "p2pb_vit_linear_f16" if half else "p2pb_vit_linear"
         attend = "p2pb_vit_attention_forward_f16" if half else "p2pb_vit_attention_forward"
 
         def linear(src, lin, weight, epi, gamma, dst):
-            call(matmul, ci(rows), ci(weight.shape[0]), ci(weight.shape[1]), ptr(src), ptr(weight), ptr(lin.bias), ci(epi),
+            call(matmul, rows, weight.shape[0], weight.shape[1], ptr(src), ptr(weight), ptr(lin.bias), epi,
                  ptr(gamma), ptr(dst), s)
 
         if hidden_states is not None:
@@ -440,7 +436,7 @@ class DinoV2(nn.Module):
                 wq, wp, w1, w2 = attn.qkv.weight, attn.proj.weight, mlp.fc1.weight, mlp.fc2.weight
             norm(t, blk.norm1, y)
             linear(y, attn.qkv, wq, EPI_BIAS, None, qkv)
-            call(attend, ci(b), ci(self.num_heads), ci(n), ci(n), ptr(qkv), ptr(y), s)
+            call(attend, b, self.num_heads, n, n, ptr(qkv), ptr(y), s)
             linear(y, attn.proj, wp, EPI_RESIDUAL, blk.ls1.gamma, t)
             norm(t, blk.norm2, y)
             linear(y, mlp.fc1, w1, EPI_GELU, None, hid)

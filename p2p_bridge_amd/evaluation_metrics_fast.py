@@ -12,7 +12,6 @@ What differs from the reference ("Set metrics"):
 CUDA tensors run the kernels (a missing library is an error, not a fallback); CPU tensors and numpy arrays take a pure torch /
 numpy path with the same arithmetic contract, which is what the host-logic tests run.
 """
-import ctypes
 import math
 import warnings
 
@@ -194,7 +193,7 @@ def _set_tensors(a, b):
 def pairwise_chamfer(a, b):
     """a [S,N,3], b [R,M,3] CUDA tensors -> f32 [S,R] of mean_p min_q + mean_q min_p (p2pb_pairwise_chamfer). Passing the same
     tensor twice takes the symmetric form (each directional sum once; the result equals its transpose bitwise)."""
-    from ._lib import call, lib, ptr, stream_ptr
+    from ._lib import ask, call, ptr, stream_ptr
 
     same = a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
                       and a.dtype == b.dtype == torch.float32)
@@ -204,24 +203,24 @@ def pairwise_chamfer(a, b):
     (s, n, _), (r, m, _) = a.shape, b.shape
     with torch.cuda.device(a.device):
         out = torch.empty(s, r, dtype=torch.float32, device=a.device)
-        ws = torch.empty(max(1, lib().p2pb_pairwise_chamfer_ws_bytes(s, r)), dtype=torch.uint8, device=a.device)
+        ws = torch.empty(max(1, ask("p2pb_pairwise_chamfer_ws_bytes", s, r)), dtype=torch.uint8, device=a.device)
         call("p2pb_pairwise_chamfer", s, r, n, m, ptr(a), ptr(b), ptr(out), ptr(ws), stream_ptr())
     return out
 
 
 def pairwise_emd(a, b, ws_bytes=None):
     """-> f32 [S,R] of earth_mover_distance_nograd(a_i, b_j) (p2pb_pairwise_emd); ws_bytes caps the scratch (pairs run in chunks)"""
-    from ._lib import call, lib, ptr, stream_ptr
+    from ._lib import ask, call, ptr, stream_ptr
 
     a, b = _set_tensors(a, b)
     (s, n, _), (r, m, _) = a.shape, b.shape
-    want = lib().p2pb_pairwise_emd_ws_bytes(s, r, n, m)
+    want = ask("p2pb_pairwise_emd_ws_bytes", s, r, n, m)
     cap = ws_bytes if ws_bytes is not None else EMD_WS_BYTES
     nbytes = max(1, want if cap is None else min(want, int(cap)))
     with torch.cuda.device(a.device):
         out = torch.empty(s, r, dtype=torch.float32, device=a.device)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
-        call("p2pb_pairwise_emd", s, r, n, m, ptr(a), ptr(b), ptr(out), ptr(ws), ctypes.c_size_t(nbytes), stream_ptr())
+        call("p2pb_pairwise_emd", s, r, n, m, ptr(a), ptr(b), ptr(out), ptr(ws), nbytes, stream_ptr())
     return out
 
 
@@ -369,18 +368,18 @@ def occupancy_counts(pclouds, resolution, in_sphere=False):
         pts = pclouds.detach().numpy() if torch.is_tensor(pclouds) else pclouds
         c, b = _occupancy_counts_host(pts, resolution, in_sphere)
         return c.astype(np.float64), b.astype(np.float64)
-    from ._lib import call, check, lib, ptr, stream_ptr
+    from ._lib import ask, call, check, ptr, stream_ptr
 
     pts = pclouds.detach().float().contiguous()
     check(pts, torch.float32, "pclouds")
-    cells = lib().p2pb_occupancy_grid_cells(int(resolution), int(bool(in_sphere)))
+    cells = ask("p2pb_occupancy_grid_cells", int(resolution), int(bool(in_sphere)))
     if cells <= 0:
         raise RuntimeError(f"occupancy grid of resolution {resolution} (in_sphere={in_sphere}) is not supported")
     expect = len(unit_cube_grid_point_cloud(resolution, in_sphere)[0].reshape(-1, 3))
     assert cells == expect, (cells, expect)  # the library's grid is numpy's grid
     with torch.cuda.device(pts.device):
         out = torch.empty(2, cells, dtype=torch.int32, device=pts.device)
-        ws = torch.empty(lib().p2pb_occupancy_ws_bytes(int(resolution)), dtype=torch.uint8, device=pts.device)
+        ws = torch.empty(ask("p2pb_occupancy_ws_bytes", int(resolution)), dtype=torch.uint8, device=pts.device)
         call("p2pb_occupancy_counts", pts.shape[0], pts.shape[1], int(resolution), int(bool(in_sphere)), ptr(pts), ptr(out[0]),
              ptr(out[1]), ptr(ws), stream_ptr())
     host = out.cpu().numpy().astype(np.float64)

@@ -7,7 +7,6 @@ Every normalisation / activation between the two convolutions and the devoxelisa
 per-(sample, channel) scale/shift vectors, so each grid tensor is written once and read once.
 Training keeps the unfused autograd graph (pvcnn_unet.PVConv.forward).
 """
-import ctypes
 import os
 
 from . import _experiment
@@ -15,9 +14,8 @@ import threading
 
 import torch
 
-from ._lib import call, check, lib, ptr, stream_ptr
+from ._lib import ask, call, check, lib, ptr, stream_ptr  # noqa: F401  (lib: tests reach the loaded library through this module)
 
-_i, _f, _d = ctypes.c_int, ctypes.c_float, ctypes.c_double
 F32 = torch.float32
 
 
@@ -57,7 +55,7 @@ def set_conv_math(name):
     if name is not None and name not in CONV_MATHS:
         raise ValueError(f"conv math must be one of {CONV_MATHS}, got {name!r}")
     _conv_math_override = name
-    rc = lib().p2pb_set_split_terms(_SPLIT_TERMS[conv_math()])
+    rc = ask("p2pb_set_split_terms", _SPLIT_TERMS[conv_math()])
     if rc != 0:
         raise RuntimeError(f"p2pb_set_split_terms -> {rc}")
     return prev
@@ -78,11 +76,11 @@ class split_math:
         # process-wide arithmetic; nesting restores the outer override
         self.prev = _split_math_depth.get(threading.get_ident(), 0)
         _split_math_depth[threading.get_ident()] = self.terms
-        lib().p2pb_set_split_terms_thread(self.terms)
+        ask("p2pb_set_split_terms_thread", self.terms)
 
     def __exit__(self, *exc):
         _split_math_depth[threading.get_ident()] = self.prev
-        lib().p2pb_set_split_terms_thread(self.prev)
+        ask("p2pb_set_split_terms_thread", self.prev)
 
 
 def pinned_math(conv):
@@ -114,7 +112,7 @@ def _honours_pin(argpos):
         def f(*a, **k):
             conv = a[argpos] if len(a) > argpos else k.get("conv")
             m = getattr(conv, "_p2pb_math", None)
-            if m is None or k.get("math") is not None or _SPLIT_TERMS[m] == lib().p2pb_get_split_terms():
+            if m is None or k.get("math") is not None or _SPLIT_TERMS[m] == ask("p2pb_get_split_terms"):
                 return fn(*a, **k)
             if k.get("pre"):
                 raise RuntimeError("a layer pinned to another arithmetic was handed a pre-split (f16x3) operand grid")
@@ -149,7 +147,7 @@ def pack_conv3d_weight(conv: torch.nn.Conv3d, split=False) -> torch.Tensor:
         cache = conv._p2pb_packed = (key, {})
     packs = cache[1]
     if split:
-        split = "f16" if lib().p2pb_get_split_terms() == 16 else "bf16"  # the pack follows the arithmetic selected now
+        split = "f16" if ask("p2pb_get_split_terms") == 16 else "bf16"  # the pack follows the arithmetic selected now
     if split not in packs:
         adjoint = bool(getattr(conv, "adjoint", False))  # dense._dgrad_holder: `w` is the forward layer's weight [ci][co]
         co, ci = (w.shape[1], w.shape[0]) if adjoint else w.shape[:2]
@@ -157,16 +155,16 @@ def pack_conv3d_weight(conv: torch.nn.Conv3d, split=False) -> torch.Tensor:
         assert split or not adjoint
         wc = w.detach().contiguous()
         if split:
-            wt = torch.empty(lib().p2pb_conv3d_k3_split_packed_bytes(_i(co), _i(ci)), dtype=torch.uint8, device=w.device)
+            wt = torch.empty(ask("p2pb_conv3d_k3_split_packed_bytes", co, ci), dtype=torch.uint8, device=w.device)
             amax = _amax_slot(w) if (split == "f16" and not adjoint) else None
             if amax is not None:
-                call("p2pb_conv3d_k3_pack_weights_split_amax", _i(co), _i(ci), ptr(wc), ptr(wt), ptr(amax), stream_ptr())
+                call("p2pb_conv3d_k3_pack_weights_split_amax", co, ci, ptr(wc), ptr(wt), ptr(amax), stream_ptr())
             else:
-                call("p2pb_conv3d_k3_pack_weights_split_adjoint" if adjoint else "p2pb_conv3d_k3_pack_weights_split", _i(co),
-                     _i(ci), ptr(wc), ptr(wt), stream_ptr())
+                call("p2pb_conv3d_k3_pack_weights_split_adjoint" if adjoint else "p2pb_conv3d_k3_pack_weights_split", co,
+                     ci, ptr(wc), ptr(wt), stream_ptr())
         else:
-            wt = torch.empty(lib().p2pb_conv3d_k3_packed_floats(_i(co), _i(ci)), dtype=F32, device=w.device)
-            call("p2pb_conv3d_k3_pack_weights", _i(co), _i(ci), ptr(wc), ptr(wt), stream_ptr())
+            wt = torch.empty(ask("p2pb_conv3d_k3_packed_floats", co, ci), dtype=F32, device=w.device)
+            call("p2pb_conv3d_k3_pack_weights", co, ci, ptr(wc), ptr(wt), stream_ptr())
         packs[split] = wt
     return packs[split]
 
@@ -176,7 +174,7 @@ def conv_pre_plan(r: int):
     grid (S format, include/p2pb_hip.h: the voxeliser / one elementwise pass apply the operand transform and the
     fp16-pair split ONCE per element, the convolution stages with LDS-DMA alone; bit-identical outputs)?
     P2PB_EXPERIMENT="conv_pre=<first>:<second>" lists resolutions, default below; f16x3 arithmetic only."""
-    if conv_math() != "f16x3" or lib().p2pb_get_split_terms() != 16:
+    if conv_math() != "f16x3" or ask("p2pb_get_split_terms") != 16:
         return False, False
     first, second = _experiment.resolution_pair("conv_pre", CONV_PRE_DEFAULT)
     return int(r) in first, int(r) in second
@@ -191,7 +189,7 @@ def conv3d_presplit(y, in_scale=None, in_shift=None, swish=False, in_sub=None):
     check(y, F32, "y")
     b, r, c = y.shape[0], y.shape[1], y.shape[4]
     out = torch.empty(b, r, r, r, (c + 15) // 16 * 16, dtype=F32, device=y.device)
-    call("p2pb_conv3d_presplit", _i(b), _i(c), ctypes.c_long(r * r * r), ptr(y), ptr(in_scale), ptr(in_shift), _i(int(swish)),
+    call("p2pb_conv3d_presplit", b, c, r * r * r, ptr(y), ptr(in_scale), ptr(in_shift), int(swish),
          ptr(in_sub), ptr(out), stream_ptr())
     return out
 
@@ -210,7 +208,7 @@ def _conv3d_prologue(x, conv, split, channels_last, pre, in_scale, in_sub, stats
     y = torch.empty(*((b, r, r, r, co) if channels_last else (b, co, r, r, r)), dtype=F32, device=x.device)
     st = None
     if stats:
-        nfl = lib().p2pb_conv3d_k3_stats_floats(_i(b), _i(co), _i(r))
+        nfl = ask("p2pb_conv3d_k3_stats_floats", b, co, r)
         st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
     return b, ci, co, r, wt, y, st
 
@@ -225,8 +223,8 @@ def conv3d_k3(x, conv, in_scale=None, in_shift=None, swish=False, stats=True, in
     split = force_split or use_split(conv.out_channels, math)
     b, ci, co, r, wt, y, st = _conv3d_prologue(x, conv, split, channels_last, pre, in_scale, in_sub, stats)
     flags = (1 if skip_zero else 0) | (2 if compact else 0) | (4 if split else 0) | (8 if channels_last else 0) | (16 if pre else 0)
-    call("p2pb_conv3d_k3_forward_ex", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias), ptr(out_class),
-         ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(in_sub), _i(flags), ptr(y), ptr(st), stream_ptr())
+    call("p2pb_conv3d_k3_forward_ex", b, ci, co, r, ptr(x), ptr(wt), ptr(conv.bias), ptr(out_class),
+         ptr(in_scale), ptr(in_shift), int(swish), ptr(in_sub), flags, ptr(y), ptr(st), stream_ptr())
     return y, st
 
 
@@ -238,7 +236,7 @@ def brick_lists(cnt, r):
     lists = torch.empty(4, b * nb, dtype=torch.int32, device=cnt.device)
     counts = torch.empty(4, dtype=torch.int32, device=cnt.device)
     flags = torch.empty(b * nb * 2, dtype=torch.uint8, device=cnt.device)
-    call("p2pb_conv3d_brick_lists", _i(b), _i(r), ptr(cnt), ptr(flags), ptr(lists), ptr(counts), stream_ptr())
+    call("p2pb_conv3d_brick_lists", b, r, ptr(cnt), ptr(flags), ptr(lists), ptr(counts), stream_ptr())
     return lists, counts
 
 
@@ -254,9 +252,8 @@ def conv3d_k3_sparse(x, conv, lists, counts, which, in_scale=None, in_shift=None
     act, ina = lists[2 * which], lists[2 * which + 1]
     ca, ci_ = counts[2 * which:], counts[2 * which + 1:]
     flags = (4 if split else 0) | (8 if channels_last else 0) | (16 if pre else 0) | (32 if active_only else 0)
-    call("p2pb_conv3d_k3_forward_sparse", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias),
-         ptr(out_class), ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(in_sub), _i(flags), ptr(act), ptr(ca),
-         ptr(ina), ptr(ci_), ptr(y), ptr(st), stream_ptr())
+    call("p2pb_conv3d_k3_forward_sparse", b, ci, co, r, ptr(x), ptr(wt), ptr(conv.bias), ptr(out_class), ptr(in_scale),
+         ptr(in_shift), int(swish), ptr(in_sub), flags, ptr(act), ptr(ca), ptr(ina), ptr(ci_), ptr(y), ptr(st), stream_ptr())
     return y, st
 
 
@@ -268,7 +265,7 @@ def active_lists(cnt, r):
     nb = {32: 128, 16: 16, 8: 2}[int(r)]
     lists = torch.empty(2, b, nb, 256, dtype=torch.uint8, device=cnt.device)
     counts = torch.empty(2, b, nb, dtype=torch.int32, device=cnt.device)
-    call("p2pb_conv3d_active_lists", _i(b), _i(int(r)), ptr(cnt), ptr(lists), ptr(counts), stream_ptr())
+    call("p2pb_conv3d_active_lists", b, int(r), ptr(cnt), ptr(lists), ptr(counts), stream_ptr())
     return lists, counts
 
 
@@ -283,12 +280,11 @@ def conv3d_k3_compact(x, conv, lists, counts, which, in_scale=None, in_shift=Non
     b, ci, co, r, wt, y, st = _conv3d_prologue(x, conv, True, True, pre, in_scale, in_sub)
     al, ac = lists[which], counts[which]
     if pre:
-        call("p2pb_conv3d_k3_forward_compact_pre", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias),
-             ptr(out_class), ptr(al), ptr(ac), ptr(y), ptr(st), _i(32 if listed_only else 0), stream_ptr())
+        call("p2pb_conv3d_k3_forward_compact_pre", b, ci, co, r, ptr(x), ptr(wt), ptr(conv.bias),
+             ptr(out_class), ptr(al), ptr(ac), ptr(y), ptr(st), 32 if listed_only else 0, stream_ptr())
         return y, st
-    call("p2pb_conv3d_k3_forward_compact", _i(b), _i(ci), _i(co), _i(r), ptr(x), ptr(wt), ptr(conv.bias),
-         ptr(out_class), ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(in_sub), ptr(al), ptr(ac), ptr(y), ptr(st),
-         _i(32 if listed_only else 0), stream_ptr())
+    call("p2pb_conv3d_k3_forward_compact", b, ci, co, r, ptr(x), ptr(wt), ptr(conv.bias), ptr(out_class), ptr(in_scale),
+         ptr(in_shift), int(swish), ptr(in_sub), ptr(al), ptr(ac), ptr(y), ptr(st), 32 if listed_only else 0, stream_ptr())
     return y, st
 
 
@@ -303,8 +299,8 @@ def conv3d_far_field(prev_bias, conv, in_scale, in_shift, swish=True):
     a = torch.empty(b, ci, dtype=F32, device=dev)
     k = torch.empty(b, 27, co, dtype=F32, device=dev)
     ws = torch.empty(b, 27, co, dtype=F32, device=dev)
-    call("p2pb_conv3d_k3_far_field", _i(b), _i(ci), _i(co), ptr(prev_bias), ptr(in_scale), ptr(in_shift),
-         _i(int(swish)), ptr(wt), ptr(conv.bias), ptr(a), ptr(k), ptr(ws), stream_ptr())
+    call("p2pb_conv3d_k3_far_field", b, ci, co, ptr(prev_bias), ptr(in_scale), ptr(in_shift),
+         int(swish), ptr(wt), ptr(conv.bias), ptr(a), ptr(k), ptr(ws), stream_ptr())
     return a, k
 
 
@@ -331,8 +327,8 @@ def conv3d_far_field_gn(prev_bias, conv, part, fin, swish=True):
     k = torch.empty(b, 27, co, dtype=F32, device=dev)
     ws = torch.empty(b, 27, co, dtype=F32, device=dev)
     style, stride = _style_arg(style, ci)
-    call("p2pb_conv3d_k3_far_field_gn", _i(b), _i(ci), _i(co), ptr(prev_bias), ptr(part), _i(nslots), _d(float(count)), _i(int(groups)),
-         ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps), _i(int(swish)), ptr(wt), ptr(conv.bias), ptr(scale), ptr(shift),
+    call("p2pb_conv3d_k3_far_field_gn", b, ci, co, ptr(prev_bias), ptr(part), nslots, float(count), int(groups),
+         ptr(gamma), ptr(beta), ptr(style), stride, eps, int(swish), ptr(wt), ptr(conv.bias), ptr(scale), ptr(shift),
          ptr(a), ptr(k), ptr(ws), stream_ptr())
     return scale, shift, a, k
 
@@ -359,9 +355,9 @@ def pvconv_tail(part2, fin2, se=None, point=None):
         stylep, stridep = _style_arg(stylep, cp)
         scp = torch.empty(b, cp, dtype=F32, device=dev)
         shp = torch.empty_like(scp)
-    call("p2pb_pvconv_tail", _i(b), _i(c), _i(hidden), ptr(part2), _i(ns2), _d(float(count2)), _i(int(groups2)), ptr(gamma2), ptr(beta2),
-         ptr(style2), _i(stride2), _f(eps2), ptr(w1), ptr(w2), ptr(aff_a), ptr(aff_b), _i(cp), ptr(partp), _i(nsp), _d(float(countp)),
-         _i(int(groupsp)), ptr(gammap), ptr(betap), ptr(stylep), _i(stridep), _f(epsp), ptr(scp), ptr(shp), stream_ptr())
+    call("p2pb_pvconv_tail", b, c, hidden, ptr(part2), ns2, float(count2), int(groups2), ptr(gamma2), ptr(beta2),
+         ptr(style2), stride2, eps2, ptr(w1), ptr(w2), ptr(aff_a), ptr(aff_b), cp, ptr(partp), nsp, float(countp),
+         int(groupsp), ptr(gammap), ptr(betap), ptr(stylep), stridep, epsp, ptr(scp), ptr(shp), stream_ptr())
     return aff_a, aff_b, scp, shp
 
 
@@ -375,8 +371,8 @@ def minmax_act_pool_gn(mm, part, fin, swish=True):
     y = torch.empty(b, c, dtype=F32, device=dev)
     scale, shift = torch.empty_like(y), torch.empty_like(y)
     style, stride = _style_arg(style, c)
-    call("p2pb_minmax_act_pool_gn", _i(b), _i(c), _i(nslots), ptr(mm), ptr(part), _i(part.shape[1]), _d(float(count)), _i(int(groups)),
-         ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps), _i(int(swish)), ptr(scale), ptr(shift), ptr(y), stream_ptr())
+    call("p2pb_minmax_act_pool_gn", b, c, nslots, ptr(mm), ptr(part), part.shape[1], float(count), int(groups),
+         ptr(gamma), ptr(beta), ptr(style), stride, eps, int(swish), ptr(scale), ptr(shift), ptr(y), stream_ptr())
     return y, scale, shift
 
 
@@ -388,8 +384,8 @@ def gn_affine_params(part, count_per_channel, groups, gamma, beta, style=None, e
     shift = torch.empty_like(scale)
     chmean = torch.empty_like(scale) if want_mean else None
     style, stride = _style_arg(style, c)
-    call("p2pb_gn_affine_params", _i(b), _i(c), _i(groups), _i(nslots), _d(float(count_per_channel)), ptr(part),
-         ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps), ptr(scale), ptr(shift), ptr(chmean), stream_ptr())
+    call("p2pb_gn_affine_params", b, c, groups, nslots, float(count_per_channel), ptr(part),
+         ptr(gamma), ptr(beta), ptr(style), stride, eps, ptr(scale), ptr(shift), ptr(chmean), stream_ptr())
     return scale, shift, chmean
 
 
@@ -397,7 +393,7 @@ def se_gate_affine(chmean, fc1_weight, fc2_weight, scale, shift):
     """SE3d gate folded into the devoxelisation affine: (scale, shift) * sigmoid(W2 relu(W1 chmean))"""
     b, c = chmean.shape
     a, bb = torch.empty_like(scale), torch.empty_like(shift)
-    call("p2pb_se_gate_affine", _i(b), _i(c), _i(fc1_weight.shape[0]), ptr(chmean), ptr(fc1_weight), ptr(fc2_weight),
+    call("p2pb_se_gate_affine", b, c, fc1_weight.shape[0], ptr(chmean), ptr(fc1_weight), ptr(fc2_weight),
          ptr(scale), ptr(shift), ptr(a), ptr(bb), stream_ptr())
     return a, bb
 
@@ -412,11 +408,11 @@ def devoxelize_affine(grid, vcoords, r, aff_a, aff_b, channels_last=False, add=N
     aff_a, aff_b = aff_a.contiguous(), aff_b.contiguous()  # (named: temporaries inside the argument list could be freed
     if channels_last:                                      #  and their blocks reused before the launch)
         h, hs, hb = add if add is not None else (None, None, None)
-        call("p2pb_trilinear_devoxelize_cl_affine", _i(b), _i(c), _i(n), _i(int(r)), ptr(vcoords), ptr(grid),
+        call("p2pb_trilinear_devoxelize_cl_affine", b, c, n, int(r), ptr(vcoords), ptr(grid),
              ptr(aff_a), ptr(aff_b), ptr(h), ptr(hs), ptr(hb), ptr(out), stream_ptr())
     else:
         assert add is None
-        call("p2pb_trilinear_devoxelize_affine", _i(b), _i(c), _i(n), _i(int(r)), ptr(vcoords), ptr(grid),
+        call("p2pb_trilinear_devoxelize_affine", b, c, n, int(r), ptr(vcoords), ptr(grid),
              ptr(aff_a), ptr(aff_b), ptr(out), stream_ptr())
     return out
 
@@ -428,8 +424,8 @@ def voxel_sort(vox, r):
     dev = vox.device
     ind = torch.empty(b, n, dtype=torch.int32, device=dev)
     cnt = torch.empty(b, r * r * r, dtype=torch.int32, device=dev)
-    ws = torch.empty(lib().p2pb_avg_voxelize_ws_bytes(_i(b), _i(n), _i(r)), dtype=torch.uint8, device=dev)
-    call("p2pb_voxel_sort", _i(b), _i(n), _i(r), ptr(vox), ptr(ind), ptr(cnt), ptr(ws), stream_ptr())
+    ws = torch.empty(ask("p2pb_avg_voxelize_ws_bytes", b, n, r), dtype=torch.uint8, device=dev)
+    call("p2pb_voxel_sort", b, n, r, ptr(vox), ptr(ind), ptr(cnt), ptr(ws), stream_ptr())
     return cnt, ws
 
 
@@ -443,11 +439,11 @@ def voxelize_cl_gather(features, cnt, ws, r, split=False):
     feat_t = torch.empty(b, n, c, dtype=F32, device=features.device)
     if split:
         out = torch.empty(b, r, r, r, (c + 15) // 16 * 16, dtype=F32, device=features.device)
-        call("p2pb_avg_voxelize_cl_gather_split", _i(b), _i(c), _i(n), _i(r), ptr(features), ptr(cnt), ptr(ws), ptr(out),
+        call("p2pb_avg_voxelize_cl_gather_split", b, c, n, r, ptr(features), ptr(cnt), ptr(ws), ptr(out),
              ptr(feat_t), stream_ptr())
         return out
     out = torch.empty(b, r, r, r, c, dtype=F32, device=features.device)
-    call("p2pb_avg_voxelize_cl_gather", _i(b), _i(c), _i(n), _i(r), ptr(features), ptr(cnt), ptr(ws), ptr(out),
+    call("p2pb_avg_voxelize_cl_gather", b, c, n, r, ptr(features), ptr(cnt), ptr(ws), ptr(out),
          ptr(feat_t), stream_ptr())
     return out
 
@@ -463,8 +459,8 @@ def voxelize_cl(features, vox, r):
     ind = torch.empty(b, n, dtype=torch.int32, device=dev)
     cnt = torch.empty(b, r * r * r, dtype=torch.int32, device=dev)
     feat_t = torch.empty(b, n, c, dtype=F32, device=dev)
-    ws = torch.empty(lib().p2pb_avg_voxelize_ws_bytes(_i(b), _i(n), _i(r)), dtype=torch.uint8, device=dev)
-    call("p2pb_avg_voxelize_cl_forward", _i(b), _i(c), _i(n), _i(r), ptr(vox), ptr(features), ptr(ind), ptr(cnt),
+    ws = torch.empty(ask("p2pb_avg_voxelize_ws_bytes", b, n, r), dtype=torch.uint8, device=dev)
+    call("p2pb_avg_voxelize_cl_forward", b, c, n, r, ptr(vox), ptr(features), ptr(ind), ptr(cnt),
          ptr(out), ptr(feat_t), ptr(ws), stream_ptr())
     return out, cnt
 
@@ -493,7 +489,7 @@ def pack_pointwise_weight(conv, ci_lo=0, ci_hi=None, split=False) -> torch.Tenso
         cache = conv._p2pb_packed_pw = (key, {})
     packs = cache[1]
     if split:
-        split = "f16" if lib().p2pb_get_split_terms() == 16 else "bf16"
+        split = "f16" if ask("p2pb_get_split_terms") == 16 else "bf16"
     k = (ci_lo, ci_hi, split)
     if k not in packs:
         if adjoint:
@@ -504,23 +500,23 @@ def pack_pointwise_weight(conv, ci_lo=0, ci_hi=None, split=False) -> torch.Tenso
             w2 = w.detach().reshape(co, -1)[:, ci_lo:ci_hi].contiguous()
         sfx = "_adjoint" if adjoint else ""
         if split:
-            wp = torch.empty(lib().p2pb_pointwise_split_packed_bytes(_i(co), _i(ci_hi - ci_lo)), dtype=torch.uint8,
+            wp = torch.empty(ask("p2pb_pointwise_split_packed_bytes", co, ci_hi - ci_lo), dtype=torch.uint8,
                              device=w.device)
             amax = _amax_slot(w) if (split == "f16" and not adjoint and ci_lo == 0 and ci_hi == w2.shape[1] == w[0].numel()) else None
             if amax is not None:
-                call("p2pb_pointwise_pack_weights_split_amax", _i(co), _i(ci_hi), ptr(w2), ptr(wp), ptr(amax), stream_ptr())
+                call("p2pb_pointwise_pack_weights_split_amax", co, ci_hi, ptr(w2), ptr(wp), ptr(amax), stream_ptr())
             else:
-                call("p2pb_pointwise_pack_weights_split" + sfx, _i(co), _i(ci_hi - ci_lo), ptr(w2), ptr(wp), stream_ptr())
+                call("p2pb_pointwise_pack_weights_split" + sfx, co, ci_hi - ci_lo, ptr(w2), ptr(wp), stream_ptr())
         else:
-            wp = torch.empty(lib().p2pb_pointwise_packed_floats(_i(co), _i(ci_hi - ci_lo)), dtype=F32, device=w.device)
-            call("p2pb_pointwise_pack_weights" + sfx, _i(co), _i(ci_hi - ci_lo), ptr(w2), ptr(wp), stream_ptr())
+            wp = torch.empty(ask("p2pb_pointwise_packed_floats", co, ci_hi - ci_lo), dtype=F32, device=w.device)
+            call("p2pb_pointwise_pack_weights" + sfx, co, ci_hi - ci_lo, ptr(w2), ptr(wp), stream_ptr())
         packs[k] = wp
     return packs[k]
 
 
 def pool_supported(npos: int, pool_u: int) -> bool:
     """can pw_conv(..., pool_u=) prepare this max-pool in its epilogue? (16-byte rows, u in 4..64 or 0 = global)"""
-    return bool(lib().p2pb_pointwise_pool_supported(_i(npos), _i(pool_u)))
+    return bool(ask("p2pb_pointwise_pool_supported", npos, pool_u))
 
 
 PW_SPLIT_MIN_CIN, PW_SPLIT_MIN_COUT = 128, 128  # measured crossover (tools/exp_pw.py)
@@ -545,13 +541,13 @@ def _fin_args(fin, b, c, device):
     arguments of the statistics-producing pointwise entry points, the style tensor they point into). The entry point puts the
     gn_affine launch right behind the producer: the values and bits of a separate gn_affine_params call, filled in stream order"""
     if fin is None:
-        return None, (_d(0.0), _i(0), ptr(None), ptr(None), ptr(None), _i(0), _f(0.0), ptr(None), ptr(None), ptr(None)), None
+        return None, (0.0, 0, ptr(None), ptr(None), ptr(None), 0, 0.0, ptr(None), ptr(None), ptr(None)), None
     count, groups, gamma, beta, style, eps, want_mean = fin
     scale = torch.empty(b, c, dtype=F32, device=device)
     shift = torch.empty_like(scale)
     chmean = torch.empty_like(scale) if want_mean else None
     style, stride = _style_arg(style, c)
-    return (scale, shift, chmean), (_d(float(count)), _i(int(groups)), ptr(gamma), ptr(beta), ptr(style), _i(stride), _f(eps),
+    return (scale, shift, chmean), (float(count), int(groups), ptr(gamma), ptr(beta), ptr(style), stride, eps,
                                     ptr(scale), ptr(shift), ptr(chmean)), style
 
 
@@ -576,36 +572,35 @@ def pw_conv(x, conv, in_scale=None, in_shift=None, swish=False, stats=True, bias
         swish = False
     point_major = point_major and not stats and pool_u is None and p % 4 == 0
     # narrow layers in the f16x3 arithmetic: the wide (register-tiled) kernel on the split pack (flags 4 | 128)
-    wide_h = (not split and math is None and conv_math() == "f16x3" and lib().p2pb_get_split_terms() == 16 and p % 4 == 0
+    wide_h = (not split and math is None and conv_math() == "f16x3" and ask("p2pb_get_split_terms") == 16 and p % 4 == 0
               and x.data_ptr() % 16 == 0 and use_wide_f16(ci, co))
     wp = pack_pointwise_weight(conv, ci_lo, ci_hi, split or wide_h)
     pre = 128 if wide_h else 0
-    flags = _i((4 if (split or wide_h) else 0) | (32 if point_major else 0) | pre)
+    flags = (4 if (split or wide_h) else 0) | (32 if point_major else 0) | pre
     if point_major:
         y = torch.empty(b, p, co, dtype=F32, device=x.device)
     else:
         y = torch.empty(b, co, p, dtype=F32, device=x.device) if (store or pool_u is None) else None
     st = None
     if stats or pool_u is not None:
-        nfl = lib().p2pb_pointwise_stats_floats(_i(b), _i(co), _i(p))
+        nfl = ask("p2pb_pointwise_stats_floats", b, co, p)
         st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=x.device)
     bias = conv.bias if use_bias else None
     # fin: the norm that follows -> the result carries (scale, shift, chmean) as well; style_kept: alive until the call returns
     aff, fin_args, style_kept = _fin_args(fin, b, co, x.device)
     if pool_u is not None:
         return _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, pool_u, b, ci, co, p, aff, fin_args)
-    call("p2pb_pointwise_conv_forward", _i(b), _i(ci), _i(co), _i(p), ptr(x), ptr(wp), ptr(bias), ptr(bias_b),
-         ptr(in_scale), ptr(in_shift), _i(int(swish)), flags, ptr(y), ptr(st), *fin_args, stream_ptr())
+    call("p2pb_pointwise_conv_forward", b, ci, co, p, ptr(x), ptr(wp), ptr(bias), ptr(bias_b),
+         ptr(in_scale), ptr(in_shift), int(swish), flags, ptr(y), ptr(st), *fin_args, stream_ptr())
     return (y, st) if fin is None else (y, st, aff)
 
 
 def _pw_conv_pool(x, wp, bias, bias_b, in_scale, in_shift, swish, flags, y, st, pool_u, b, ci, co, p, aff, fin_args):
-    nmm = lib().p2pb_pointwise_minmax_floats(_i(b), _i(co), _i(p), _i(pool_u), flags)
+    nmm = ask("p2pb_pointwise_minmax_floats", b, co, p, pool_u, flags)
     mm = torch.empty((b, nmm // (b * co * 2), co, 2) if pool_u == 0 else (b, co, p // pool_u, 2), dtype=F32,
                      device=x.device)
-    call("p2pb_pointwise_conv_pool_forward", _i(b), _i(ci), _i(co), _i(p), ptr(x), ptr(wp), ptr(bias), ptr(bias_b),
-         ptr(in_scale), ptr(in_shift), _i(int(swish)), flags, ptr(y), ptr(st), _i(pool_u), ptr(mm), *fin_args,
-         stream_ptr())
+    call("p2pb_pointwise_conv_pool_forward", b, ci, co, p, ptr(x), ptr(wp), ptr(bias), ptr(bias_b), ptr(in_scale), ptr(in_shift),
+         int(swish), flags, ptr(y), ptr(st), pool_u, ptr(mm), *fin_args, stream_ptr())
     return (y, st, mm) if aff is None else (y, st, mm, aff)
 
 
@@ -621,8 +616,8 @@ def linear_rows(x, weight, bias=None):
     co = weight.shape[0]
     assert weight.shape[1] == ci and x.dtype == F32 and weight.dtype == F32 and x.is_cuda
     out = torch.empty(b, co, dtype=F32, device=x.device)
-    call("p2pb_linear_rows", _i(b), _i(ci), _i(co), ptr(x), ctypes.c_long(x.stride(0)), ptr(weight), ctypes.c_long(weight.stride(0)),
-         ptr(bias), ptr(out), ctypes.c_long(co), stream_ptr())
+    call("p2pb_linear_rows", b, ci, co, ptr(x), x.stride(0), ptr(weight), weight.stride(0),
+         ptr(bias), ptr(out), co, stream_ptr())
     return out
 
 
@@ -637,7 +632,7 @@ def minmax_act(mm, scale, shift, swish=True, global_pool=False):
         b, c, m, _ = mm.shape
         nslots = 0
         y = torch.empty(b, c, m, dtype=F32, device=mm.device)
-    call("p2pb_minmax_act", _i(b), _i(c), _i(m), _i(nslots), ptr(mm), ptr(scale), ptr(shift), _i(int(swish)), ptr(y),
+    call("p2pb_minmax_act", b, c, m, nslots, ptr(mm), ptr(scale), ptr(shift), int(swish), ptr(y),
          stream_ptr())
     return y
 
@@ -645,7 +640,7 @@ def minmax_act(mm, scale, shift, swish=True, global_pool=False):
 def gather_pool_supported(ci: int, co: int, m: int, u: int) -> bool:
     """can pw_conv_pool_gather run the last set-abstraction layer ci -> co over (m centres x u neighbours) on the gathered
     operand? (the narrow-layer f16x3 kernel: not the LDS-tiled GEMM's shapes; 32-byte row pieces; a supported pool)"""
-    return (conv_math() == "f16x3" and lib().p2pb_get_split_terms() == 16 and ci % 8 == 0
+    return (conv_math() == "f16x3" and ask("p2pb_get_split_terms") == 16 and ci % 8 == 0
             and not use_split_pw(ci, co, m * u) and use_wide_f16(ci, co) and pool_supported(m * u, u) and u > 0
             and _experiment.get("sa_gather", "1") != "0")
 
@@ -662,12 +657,12 @@ def pw_conv_pool_gather(zt, cxt, idx, conv, in_scale, in_shift, swish=True, fin=
     co = conv.weight.shape[0]
     p = m * u
     wp = pack_pointwise_weight(conv, 0, None, True)
-    nfl = lib().p2pb_pointwise_stats_floats(_i(b), _i(co), _i(p))
+    nfl = ask("p2pb_pointwise_stats_floats", b, co, p)
     st = torch.empty(b, nfl // (b * co * 2), co, 2, dtype=F32, device=zt.device)
     mm = torch.empty(b, co, m, 2, dtype=F32, device=zt.device)
     aff, fin_args, style_kept = _fin_args(fin, b, co, zt.device)  # (style_kept: alive until the call returns)
-    call("p2pb_pointwise_conv_pool_gather", _i(b), _i(ci), _i(co), _i(n), _i(m), _i(u), ptr(zt), ptr(cxt), ptr(idx), ptr(wp),
-         ptr(conv.bias), ptr(in_scale), ptr(in_shift), _i(int(swish)), ptr(st), ptr(mm), *fin_args, stream_ptr())
+    call("p2pb_pointwise_conv_pool_gather", b, ci, co, n, m, u, ptr(zt), ptr(cxt), ptr(idx), ptr(wp),
+         ptr(conv.bias), ptr(in_scale), ptr(in_shift), int(swish), ptr(st), ptr(mm), *fin_args, stream_ptr())
     return (st, mm) if fin is None else (st, mm, aff)
 
 
@@ -684,15 +679,14 @@ def group_sub(z, cx, idx, point_major=False, stats_only=False):
     m, u = idx.shape[1], idx.shape[2]
     # stats_only: only the GroupNorm partials of the grouped tensor (the consumer gathers it itself: pw_conv_pool_gather)
     if stats_only and point_major:  # lane = channel, no transpose, slots of 128 positions (csrc/neighbors.hip group_stats_kernel)
-        st = torch.empty(b, lib().p2pb_group_sub_stats_slots(_i(m), _i(u)), c, 2, dtype=F32, device=z.device)
-        call("p2pb_group_sub_stats", _i(b), _i(c), _i(n), _i(m), _i(u), ptr(z), ptr(cx), ptr(idx), ptr(st), stream_ptr())
+        st = torch.empty(b, ask("p2pb_group_sub_stats_slots", m, u), c, 2, dtype=F32, device=z.device)
+        call("p2pb_group_sub_stats", b, c, n, m, u, ptr(z), ptr(cx), ptr(idx), ptr(st), stream_ptr())
         return None, st
     y = None if stats_only else torch.empty(b, c, m * u, dtype=F32, device=z.device)
-    nfl = lib().p2pb_group_sub_stats_floats(_i(b), _i(c), _i(m), _i(u))
+    nfl = ask("p2pb_group_sub_stats_floats", b, c, m, u)
     st = torch.empty(b, nfl // (b * c * 2), c, 2, dtype=F32, device=z.device)
     ws = None if point_major else torch.empty(b * (n + m) * c, dtype=F32, device=z.device)
-    call("p2pb_group_sub", _i(b), _i(c), _i(n), _i(m), _i(u), ptr(z), ptr(cx), ptr(idx), ptr(y), ptr(st), ptr(ws),
-         stream_ptr())
+    call("p2pb_group_sub", b, c, n, m, u, ptr(z), ptr(cx), ptr(idx), ptr(y), ptr(st), ptr(ws), stream_ptr())
     return y, st
 
 
@@ -706,10 +700,10 @@ def interp_add(cz, idx, w, add=None, bias=None, point_major=False):
         b, c, m = cz.shape
     n = idx.shape[2]
     y = torch.empty(b, c, n, dtype=F32, device=cz.device)
-    nfl = lib().p2pb_group_sub_stats_floats(_i(b), _i(c), _i(n), _i(1))
+    nfl = ask("p2pb_group_sub_stats_floats", b, c, n, 1)
     st = torch.empty(b, nfl // (b * c * 2), c, 2, dtype=F32, device=cz.device)
     ws = None if point_major else torch.empty(b * m * c, dtype=F32, device=cz.device)
-    call("p2pb_three_interpolate_add", _i(b), _i(c), _i(m), _i(n), ptr(cz), ptr(idx), ptr(w), ptr(add), ptr(bias),
+    call("p2pb_three_interpolate_add", b, c, m, n, ptr(cz), ptr(idx), ptr(w), ptr(add), ptr(bias),
          ptr(y), ptr(st), ptr(ws), stream_ptr())
     return y, st
 
@@ -720,7 +714,7 @@ def affine_act(x, scale, shift, swish=True, residual=None):
     y = torch.empty_like(x)
     if residual is not None:
         residual = residual.contiguous()
-    call("p2pb_affine_act", _i(b), _i(c), _i(p), ptr(x), ptr(scale), ptr(shift), _i(int(swish)), ptr(residual), ptr(y),
+    call("p2pb_affine_act", b, c, p, ptr(x), ptr(scale), ptr(shift), int(swish), ptr(residual), ptr(y),
          stream_ptr())
     return y
 
@@ -736,7 +730,7 @@ def affine_act_max(x, scale, shift, m, u, swish=True):
     u == 0: max over the whole row -> f32[B,C]"""
     b, c = x.shape[:2]
     y = torch.empty((b, c, m) if u else (b, c), dtype=F32, device=x.device)
-    call("p2pb_affine_act_max", _i(b), _i(c), _i(m), _i(u), ptr(x), ptr(scale), ptr(shift), _i(int(swish)), ptr(y),
+    call("p2pb_affine_act_max", b, c, m, u, ptr(x), ptr(scale), ptr(shift), int(swish), ptr(y),
          stream_ptr())
     return y
 

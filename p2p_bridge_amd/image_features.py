@@ -24,14 +24,13 @@ Deviations from the reference, all deliberate:
   * the DINOv2 model is `dinov2.DinoV2` from a checkpoint file, or the caller's (`feature_fn`): torch.hub is a download;
   * COLMAP text, the pose JSON and the PNGs are read by the caller.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ._lib import call, lib, ptr, stream_ptr
+from ._lib import ask, call, ptr, stream_ptr
 
 F16, F32, F64, I32, U8 = torch.float16, torch.float32, torch.float64, torch.int32, torch.uint8
 KNN_WS_BYTES = 1 << 30  # scratch of one p2pb_knn_points launch: the missing points are taken in chunks of this size
@@ -151,11 +150,10 @@ def visible_points(points, rotation, translation, camera_matrix, width, height, 
         return _back(valid, like), _back(xy, like)
     valid = torch.empty(b, n, dtype=U8, device=dev)
     xy = torch.empty(b, n, 2, dtype=I32, device=dev)
-    args = (ctypes.c_int(b), ctypes.c_int(n), ctypes.c_int(width), ctypes.c_int(height))
-    ws = torch.empty(int(lib().p2pb_imgfeat_visibility_ws_bytes(*args)), dtype=U8, device=dev)
-    call("p2pb_imgfeat_visibility", ctypes.c_int(b), ctypes.c_int(n), ptr(points), ptr(rotation), ptr(translation),
-         ptr(camera_matrix), ctypes.c_int(width), ctypes.c_int(height), ctypes.c_double(min_depth), ctypes.c_double(max_depth),
-         ptr(valid), ptr(xy), ptr(ws), stream_ptr())
+    args = (b, n, width, height)
+    ws = torch.empty(int(ask("p2pb_imgfeat_visibility_ws_bytes", *args)), dtype=U8, device=dev)
+    call("p2pb_imgfeat_visibility", b, n, ptr(points), ptr(rotation), ptr(translation), ptr(camera_matrix), width, height,
+         min_depth, max_depth, ptr(valid), ptr(xy), ptr(ws), stream_ptr())
     return valid.view(torch.bool), xy
 
 
@@ -201,8 +199,7 @@ def update_features(mean, count, maps, valid, xy):
     if dev.type != "cuda":
         update_features_torch(mean, count, maps, valid, xy)
         return out
-    call("p2pb_imgfeat_fuse", ctypes.c_int(b), ctypes.c_int(n), ctypes.c_int(c), ctypes.c_int(hmap), ctypes.c_int(wmap),
-         ptr(maps), ptr(valid.view(U8)), ptr(xy), ptr(mean), ptr(count), stream_ptr())
+    call("p2pb_imgfeat_fuse", b, n, c, hmap, wmap, ptr(maps), ptr(valid.view(U8)), ptr(xy), ptr(mean), ptr(count), stream_ptr())
     return out
 
 
@@ -257,8 +254,7 @@ def sample_grid(grid, out_size, xy):
     if dev.type != "cuda":
         return _back(sample_grid_torch(grid, (out_h, out_w), xy), like)
     out = torch.empty(b, n, c, dtype=F16, device=dev)
-    ci = ctypes.c_int
-    call("p2pb_imgfeat_sample_grid", ci(b), ci(n), ci(c), ci(h), ci(w), ci(out_h), ci(out_w), ptr(grid), ptr(xy), ptr(out),
+    call("p2pb_imgfeat_sample_grid", b, n, c, h, w, out_h, out_w, ptr(grid), ptr(xy), ptr(out),
          stream_ptr())
     return out
 
@@ -294,8 +290,7 @@ def update_features_from_grid(mean, count, grid, out_size, valid, xy):
     if dev.type != "cuda":
         update_features_from_grid_torch(mean, count, grid, (out_h, out_w), valid, xy)
         return out
-    ci = ctypes.c_int
-    call("p2pb_imgfeat_fuse_grid", ci(b), ci(n), ci(c), ci(h), ci(w), ci(out_h), ci(out_w), ptr(grid), ptr(valid.view(U8)),
+    call("p2pb_imgfeat_fuse_grid", b, n, c, h, w, out_h, out_w, ptr(grid), ptr(valid.view(U8)),
          ptr(xy), ptr(mean), ptr(count), stream_ptr())
     return out
 
@@ -339,11 +334,11 @@ def _fill_hip(feats, count, points, k):
     cloud = points.float().reshape(1, n, 3).contiguous()
     nbr = torch.empty(m, k, dtype=I32, device=dev)
     step = max(1, min(m, KNN_WS_BYTES // (4 * n)))
-    ws = torch.empty(int(lib().p2pb_knn_points_ws_bytes(ctypes.c_int(1), ctypes.c_int(step), ctypes.c_int(n))), dtype=U8, device=dev)
+    ws = torch.empty(int(ask("p2pb_knn_points_ws_bytes", 1, step, n)), dtype=U8, device=dev)
     for m0 in range(0, m, step):
         s = min(step, m - m0)
         query = cloud[0, missing[m0:m0 + s].long()].contiguous()
-        call("p2pb_knn_points", ctypes.c_int(1), ctypes.c_int(s), ctypes.c_int(n), ctypes.c_int(k), ptr(query), ptr(cloud),
+        call("p2pb_knn_points", 1, s, n, k, ptr(query), ptr(cloud),
              None, ptr(nbr[m0:m0 + s]), None, ptr(ws), stream_ptr())
     done_round = torch.zeros(n, dtype=I32, device=dev)
     remaining = torch.zeros(1, dtype=I32, device=dev)
@@ -351,8 +346,8 @@ def _fill_hip(feats, count, points, k):
     left, rounds = m, 0
     while left > 0:
         rounds += 1
-        call("p2pb_imgfeat_fill_round", ctypes.c_int(m), ctypes.c_int(n), ctypes.c_int(c), ctypes.c_int(k), ptr(missing),
-             ptr(nbr), ptr(count), ptr(feats), ptr(done_round), ctypes.c_int(rounds), ptr(remaining), stream_ptr())
+        call("p2pb_imgfeat_fill_round", m, n, c, k, ptr(missing),
+             ptr(nbr), ptr(count), ptr(feats), ptr(done_round), rounds, ptr(remaining), stream_ptr())
         now = int(remaining.item())
         if not 0 <= now < left:  # (the lowest unfinished point is always ready: every round finishes at least one)
             raise RuntimeError(f"interpolate_missing_features: round {rounds} left {now} of {left} points")

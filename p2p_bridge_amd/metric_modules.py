@@ -8,14 +8,12 @@
 Same argument order, ownership (chamfer/auction write into caller-allocated tensors) and return
 conventions (chamfer 1/0, auction 1/-1) as the reference's pybind functions.
 """
-import ctypes
 import types
 
 import torch
 
-from ._lib import P2PBError, call, check, lib, ptr, stream_ptr
+from ._lib import P2PBError, ask, call, check, ptr, stream_ptr
 
-_i, _f = ctypes.c_int, ctypes.c_float
 F32, I32 = torch.float32, torch.int32
 
 
@@ -25,8 +23,8 @@ def _chamfer_forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
     check(idx1, I32, "idx1"), check(idx2, I32, "idx2")
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    ws = torch.empty(int(lib().p2pb_chamfer_ws_bytes(_i(b), _i(n), _i(m))), dtype=torch.uint8, device=xyz1.device)
-    rc = lib().p2pb_chamfer_forward_ws(_i(b), _i(n), _i(m), ptr(xyz1), ptr(xyz2), ptr(dist1), ptr(dist2), ptr(idx1),
+    ws = torch.empty(int(ask("p2pb_chamfer_ws_bytes", b, n, m)), dtype=torch.uint8, device=xyz1.device)
+    rc = ask("p2pb_chamfer_forward_ws", b, n, m, ptr(xyz1), ptr(xyz2), ptr(dist1), ptr(dist2), ptr(idx1),
                                        ptr(idx2), ptr(ws), stream_ptr())
     return 1 if rc == 0 else 0
 
@@ -37,7 +35,7 @@ def _chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1
         check(t, F32, n_)
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    rc = lib().p2pb_chamfer_backward(_i(b), _i(n), _i(m), ptr(xyz1), ptr(xyz2), ptr(gradxyz1), ptr(gradxyz2),
+    rc = ask("p2pb_chamfer_backward", b, n, m, ptr(xyz1), ptr(xyz2), ptr(gradxyz1), ptr(gradxyz2),
                                      ptr(graddist1), ptr(graddist2), ptr(idx1), ptr(idx2), stream_ptr())
     return 1 if rc == 0 else 0
 
@@ -84,9 +82,8 @@ def _approxmatch_forward(xyz1, xyz2):
     if xyz2.shape[0] != b or d != 3 or xyz2.shape[2] != 3:
         raise RuntimeError("Check failed: shapes")  # CHECK_EQ in emd_kernel.cu:184-186
     match = torch.empty(b, m, n, dtype=F32, device=xyz1.device)
-    temp = torch.empty(int(lib().p2pb_approxmatch_temp_floats(_i(b), _i(n), _i(m))), dtype=F32, device=xyz1.device)
-    call("p2pb_approxmatch_forward_ws", _i(b), _i(n), _i(m), ptr(xyz1), ptr(xyz2), ptr(match), ptr(temp),
-         ctypes.c_size_t(temp.numel()), stream_ptr())
+    temp = torch.empty(int(ask("p2pb_approxmatch_temp_floats", b, n, m)), dtype=F32, device=xyz1.device)
+    call("p2pb_approxmatch_forward_ws", b, n, m, ptr(xyz1), ptr(xyz2), ptr(match), ptr(temp), temp.numel(), stream_ptr())
     return match
 
 
@@ -95,7 +92,7 @@ def _matchcost_forward(xyz1, xyz2, match):
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
     cost = torch.empty(b, dtype=F32, device=xyz1.device)
-    call("p2pb_matchcost_forward", _i(b), _i(n), _i(m), ptr(xyz1), ptr(xyz2), ptr(match), ptr(cost), stream_ptr())
+    call("p2pb_matchcost_forward", b, n, m, ptr(xyz1), ptr(xyz2), ptr(match), ptr(cost), stream_ptr())
     return cost
 
 
@@ -106,8 +103,7 @@ def _matchcost_backward(grad_cost, xyz1, xyz2, match):
     m = xyz2.shape[1]
     g1 = torch.empty(b, n, 3, dtype=F32, device=xyz1.device)
     g2 = torch.empty(b, m, 3, dtype=F32, device=xyz1.device)
-    call("p2pb_matchcost_backward", _i(b), _i(n), _i(m), ptr(grad_cost), ptr(xyz1), ptr(xyz2), ptr(match), ptr(g1),
-         ptr(g2), stream_ptr())
+    call("p2pb_matchcost_backward", b, n, m, ptr(grad_cost), ptr(xyz1), ptr(xyz2), ptr(match), ptr(g1), ptr(g2), stream_ptr())
     return [g1, g2]
 
 
@@ -122,10 +118,9 @@ def _auction_forward(xyz1, xyz2, dist, assignment, price, assignment_inv, bid, b
     check(xyz1, F32, "xyz1"), check(xyz2, F32, "xyz2")
     b, n, _ = xyz1.shape
     m = xyz2.shape[1]
-    rc = lib().p2pb_auction_forward(_i(b), _i(n), _i(m), ptr(xyz1), ptr(xyz2), ptr(dist), ptr(assignment), ptr(price),
-                                    ptr(assignment_inv), ptr(bid), ptr(bid_increments), ptr(max_increments),
-                                    ptr(unass_idx), ptr(unass_cnt), ptr(unass_cnt_sum), ptr(cnt_tmp), ptr(max_idx),
-                                    _f(eps), _i(int(iters)), stream_ptr())
+    rc = ask("p2pb_auction_forward", b, n, m, ptr(xyz1), ptr(xyz2), ptr(dist), ptr(assignment), ptr(price), ptr(assignment_inv),
+             ptr(bid), ptr(bid_increments), ptr(max_increments), ptr(unass_idx), ptr(unass_cnt), ptr(unass_cnt_sum), ptr(cnt_tmp),
+             ptr(max_idx), eps, int(iters), stream_ptr())
     if rc == -1:
         print("Input Error! (emd_assignment: n == m, n % 128 == 0, batch <= 512 required)")
     return rc
@@ -133,7 +128,7 @@ def _auction_forward(xyz1, xyz2, dist, assignment, price, assignment_inv, bid, b
 
 def _auction_backward(xyz1, xyz2, gradxyz, graddist, idx):
     b, n, _ = xyz1.shape
-    return lib().p2pb_auction_backward(_i(b), _i(n), ptr(xyz1), ptr(xyz2), ptr(gradxyz), ptr(graddist), ptr(idx),
+    return ask("p2pb_auction_backward", b, n, ptr(xyz1), ptr(xyz2), ptr(gradxyz), ptr(graddist), ptr(idx),
                                        stream_ptr())
 
 

@@ -264,13 +264,11 @@ _DEFAULT_MIN_TRIANGLE_AREA = 5e-3  # pytorch3d.loss.point_mesh_distance
 
 def _p2m(fn, points, tris, n_out, min_triangle_area):
     from ._lib import call, check, ptr, stream_ptr
-    import ctypes
 
     check(points, torch.float32, "points"), check(tris, torch.float32, "tris")
     d = torch.empty(n_out, dtype=torch.float32, device=points.device)
     idx = torch.empty(n_out, dtype=torch.int32, device=points.device)
-    call(fn, ctypes.c_int(points.shape[0]), ctypes.c_int(tris.shape[0]), ptr(points), ptr(tris),
-         ctypes.c_float(min_triangle_area), ptr(d), ptr(idx), stream_ptr())
+    call(fn, points.shape[0], tris.shape[0], ptr(points), ptr(tris), min_triangle_area, ptr(d), ptr(idx), stream_ptr())
     return d, idx.long()
 
 

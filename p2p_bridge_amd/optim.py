@@ -9,7 +9,6 @@ clip_grad_norm_), the step count and learning rate live in a device control bloc
 follows a scheduler, and `skip_nonfinite` gives the GradScaler behaviour (a non-finite gradient norm skips the update)
 without its host synchronisation.
 """
-import ctypes
 from typing import List, Optional
 
 import numpy as np
@@ -66,9 +65,8 @@ class ClipAdamW(torch.optim.Optimizer):
         key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in ps)
         if key == self._key:
             return
-        lib = _lib.lib()
-        ch = int(lib.p2pb_optim_chunk())
-        assert int(lib.p2pb_optim_entry_bytes()) == 40
+        ch = int(_lib.ask("p2pb_optim_chunk"))
+        assert int(_lib.ask("p2pb_optim_entry_bytes")) == 40
         tab = np.empty((len(ps), 5), dtype=np.int64)
         chunks = []
         for i, p in enumerate(ps):
@@ -130,8 +128,8 @@ class ClipAdamW(torch.optim.Optimizer):
         self._tables(ps)
         b1, b2 = group["betas"]
         _lib.call("p2pb_optim_clip_adam_step", int(self._partial.numel()), _lib.ptr(self._tab), _lib.ptr(self._chunks),
-                  _lib.ptr(self._partial), _lib.ptr(ctl), ctypes.c_double(self.max_norm), ctypes.c_double(b1), ctypes.c_double(b2),
-                  ctypes.c_double(group["eps"]), ctypes.c_double(group["weight_decay"]), int(self.decoupled),
+                  _lib.ptr(self._partial), _lib.ptr(ctl), self.max_norm, b1, b2,
+                  group["eps"], group["weight_decay"], int(self.decoupled),
                   int(self.skip_nonfinite), _lib.ptr(self._amax), int(self._amax.numel()), _lib.stream_ptr())
         self.bump_versions(ps)
         return loss

@@ -13,13 +13,12 @@ Inside `p2p_bridge_amd.deterministic()` the target rows of every backward pass a
 target over lists built here with a stable sort); outside it they are fp32 atomic adds. Contract: include/p2pb_hip.h,
 "point-to-mesh, packed batches with gradients".
 """
-import ctypes
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from ._lib import call, check, lib, ptr, stream_ptr
+from ._lib import ask, call, check, ptr, stream_ptr
 
 _DEFAULT_MIN_TRIANGLE_AREA: float = 5e-3
 
@@ -68,9 +67,8 @@ def _forward(kind, points, points_first_idx, prims, prims_first_idx, max_queries
     nq = np_ if kind[1] else ns
     dists = torch.empty(nq, dtype=torch.float32, device=points.device)
     idxs = torch.empty(nq, dtype=torch.int64, device=points.device)
-    call("p2pb_p2m_packed_forward", ctypes.c_int(kind[0]), ctypes.c_int(len(cp)), ctypes.c_int(np_), ctypes.c_int(ns),
-         ctypes.c_int(max_queries), ptr(points), ptr(points_first_idx), ptr(prims), ptr(prims_first_idx),
-         ctypes.c_float(min_triangle_area), ptr(dists), ptr(idxs), stream_ptr())
+    call("p2pb_p2m_packed_forward", kind[0], len(cp), np_, ns, max_queries, ptr(points), ptr(points_first_idx), ptr(prims),
+         ptr(prims_first_idx), min_triangle_area, ptr(dists), ptr(idxs), stream_ptr())
     return dists, idxs
 
 
@@ -82,7 +80,7 @@ def _backward(kind, points, prims, idxs, grad_dists, min_triangle_area):
     if tuple(idxs.shape) != (nq,) or tuple(grad_dists.shape) != (nq,):
         raise ValueError(f"idxs and grad_dists must be [{nq}], got {tuple(idxs.shape)} and {tuple(grad_dists.shape)}")
     order = start = None
-    if lib().p2pb_get_deterministic():
+    if ask("p2pb_get_deterministic"):
         # target -> queries lists (plumbing): the queries sorted by their target, ties in ascending query index, and where every
         # target's run begins. The kernel then WRITES every target row, so nothing is zero-filled.
         sorted_idx, order = torch.sort(idxs, stable=True)
@@ -92,9 +90,8 @@ def _backward(kind, points, prims, idxs, grad_dists, min_triangle_area):
         grad_points, grad_prims = torch.empty_like(points), torch.zeros_like(prims)
     else:
         grad_points, grad_prims = torch.zeros_like(points), torch.empty_like(prims)
-    call("p2pb_p2m_packed_backward", ctypes.c_int(kind[0]), ctypes.c_int(np_), ctypes.c_int(ns), ptr(points), ptr(prims),
-         ptr(idxs), ptr(grad_dists), ctypes.c_float(min_triangle_area), ptr(order), ptr(start), ptr(grad_points),
-         ptr(grad_prims), stream_ptr())
+    call("p2pb_p2m_packed_backward", kind[0], np_, ns, ptr(points), ptr(prims), ptr(idxs), ptr(grad_dists), min_triangle_area,
+         ptr(order), ptr(start), ptr(grad_points), ptr(grad_prims), stream_ptr())
     return grad_points, grad_prims
 
 

@@ -53,14 +53,6 @@ def workspace_bound_bytes(n_points, n_tris):
     return 42 * int(n_tris) + 12 * plan_inc + 24 * int(n_points)
 
 
-def _i(v):
-    return ctypes.c_int(int(v))
-
-
-def _f(v):
-    return ctypes.c_float(float(v))
-
-
 def _f32(v):
     return ctypes.c_float(float(v)).value
 
@@ -103,7 +95,7 @@ class TriangleGrid:
         self.plan = plan
         if not plan.usable:
             return
-        call("p2pb_p2m_grid_classify", _i(T), ptr(tris), _f(min_triangle_area), _f(plan.mag), ptr(self.box),
+        call("p2pb_p2m_grid_classify", int(T), ptr(tris), float(min_triangle_area), float(plan.mag), ptr(self.box),
              ptr(self.shrink_t), ptr(self.cls), stream_ptr())
         prunable = self.cls == 0
         self.n_unbounded = T - int(prunable.sum())
@@ -117,7 +109,7 @@ class TriangleGrid:
         wide = torch.empty(T, dtype=torch.uint8, device=dev)
         cell = plan.cell
         for _ in range(24):  # enlarge the cell rather than exceed the workspace bound
-            call("p2pb_p2m_grid_count", _i(T), ptr(self.cls), ptr(self.box), _f(cell), _i(plan.cap), ptr(counts), ptr(wide),
+            call("p2pb_p2m_grid_count", int(T), ptr(self.cls), ptr(self.box), float(cell), int(plan.cap), ptr(counts), ptr(wide),
                  stream_ptr())
             total = int(counts.sum(dtype=torch.int64))
             if total <= plan.max_incidences:
@@ -134,8 +126,8 @@ class TriangleGrid:
             offsets = torch.cumsum(counts, 0, dtype=torch.int64) - counts
             keys = torch.empty(total, dtype=torch.int64, device=dev)
             ids = torch.empty(total, dtype=torch.int32, device=dev)
-            call("p2pb_p2m_grid_fill", _i(T), ptr(counts), ptr(offsets), ptr(self.box), _f(self.plan.cell),
-                 ctypes.c_longlong(total), ptr(keys), ptr(ids), stream_ptr())
+            call("p2pb_p2m_grid_fill", int(T), ptr(counts), ptr(offsets), ptr(self.box), float(self.plan.cell),
+                 total, ptr(keys), ptr(ids), stream_ptr())
             self.keys, perm = torch.sort(keys)
             self.ids = ids[perm].contiguous()
 
@@ -160,7 +152,7 @@ class TriangleGrid:
 
         d = torch.empty(n_out, dtype=torch.float32, device=points.device)
         idx = torch.empty(n_out, dtype=torch.int32, device=points.device)
-        call(fn, _i(points.shape[0]), _i(self.n_tris), ptr(points), ptr(self.tris), _f(self.min_triangle_area), ptr(d),
+        call(fn, int(points.shape[0]), int(self.n_tris), ptr(points), ptr(self.tris), float(self.min_triangle_area), ptr(d),
              ptr(idx), stream_ptr())
         return d, idx
 
@@ -174,8 +166,8 @@ class TriangleGrid:
         if 2 * nleft > n:
             d, idx = self._brute("p2pb_point_face_dist" if which == 0 else "p2pb_face_point_dist", points, n)
         elif nleft:
-            call("p2pb_p2m_point_face_subset" if which == 0 else "p2pb_p2m_face_point_subset", _i(nleft), ptr(left),
-                 _i(points.shape[0]), _i(self.n_tris), ptr(points), ptr(self.tris), _f(self.min_triangle_area), ptr(d),
+            call("p2pb_p2m_point_face_subset" if which == 0 else "p2pb_p2m_face_point_subset", int(nleft), ptr(left),
+                 int(points.shape[0]), int(self.n_tris), ptr(points), ptr(self.tris), float(self.min_triangle_area), ptr(d),
                  ptr(idx), stream_ptr())
         out = (d, idx.long())
         return out + (self._stats(nleft, n),) if return_stats else out
@@ -193,9 +185,9 @@ class TriangleGrid:
         idx = torch.empty(P, dtype=torch.int32, device=dev)
         unresolved = torch.empty(P, dtype=torch.uint8, device=dev)
         pl = self.plan
-        call("p2pb_p2m_grid_point_face", _i(P), _i(self.n_tris), _i(self.n_inc), _i(self.n_wide), _i(pl.max_ring), ptr(points),
-             ptr(self.tris), _f(self.min_triangle_area), ptr(self.keys), ptr(self.ids),
-             ptr(self.wide_ids if self.n_wide else None), _f(pl.cell), _f(pl.mag), _f(self.shrink), ptr(d), ptr(idx),
+        call("p2pb_p2m_grid_point_face", int(P), int(self.n_tris), int(self.n_inc), int(self.n_wide), int(pl.max_ring), ptr(points),
+             ptr(self.tris), float(self.min_triangle_area), ptr(self.keys), ptr(self.ids),
+             ptr(self.wide_ids if self.n_wide else None), float(pl.cell), float(pl.mag), float(self.shrink), ptr(d), ptr(idx),
              ptr(unresolved), stream_ptr())
         return self._finish(0, points, d, idx, unresolved, return_stats)
 
@@ -221,7 +213,7 @@ class TriangleGrid:
             sub = points[sel].contiguous()
             keys = torch.empty(ns, dtype=torch.int64, device=dev)
             bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            call("p2pb_scan_cell_keys", _i(ns), ptr(sub), _f(pl.cell), ptr(keys), ptr(bad), stream_ptr())
+            call("p2pb_scan_cell_keys", int(ns), ptr(sub), float(pl.cell), ptr(keys), ptr(bad), stream_ptr())
             skeys, perm = torch.sort(keys)
             spts = sub[perm].contiguous()
             order = sel[perm].to(torch.int32).contiguous()
@@ -232,8 +224,8 @@ class TriangleGrid:
         d = torch.empty(T, dtype=torch.float32, device=dev)
         idx = torch.empty(T, dtype=torch.int32, device=dev)
         unresolved = torch.empty(T, dtype=torch.uint8, device=dev)
-        call("p2pb_p2m_grid_face_point", _i(ns), _i(T), _i(nextra), _i(pl.max_ring), _i(pl.max_cols), ptr(spts), ptr(order),
-             ptr(skeys), ptr(extra), ptr(out_idx if nextra else None), ptr(self.tris), _f(self.min_triangle_area),
-             ptr(self.cls), ptr(self.box), _f(pl.cell), _f(pl.mag), _f(self.shrink), ptr(d), ptr(idx), ptr(unresolved),
+        call("p2pb_p2m_grid_face_point", int(ns), int(T), int(nextra), int(pl.max_ring), int(pl.max_cols), ptr(spts), ptr(order),
+             ptr(skeys), ptr(extra), ptr(out_idx if nextra else None), ptr(self.tris), float(self.min_triangle_area),
+             ptr(self.cls), ptr(self.box), float(pl.cell), float(pl.mag), float(self.shrink), ptr(d), ptr(idx), ptr(unresolved),
              stream_ptr())
         return self._finish(1, points, d, idx, unresolved, return_stats)

@@ -11,9 +11,8 @@ import torch
 
 from . import _experiment
 
-from ._lib import P2PBError, call, check, lib, ptr, stream_ptr
+from ._lib import P2PBError, ask, call, check, lib, ptr, stream_ptr  # noqa: F401  (lib: tests reach the loaded library through this module)
 
-_i, _f = ctypes.c_int, ctypes.c_float
 F32, I32 = torch.float32, torch.int32
 
 
@@ -28,8 +27,7 @@ def voxel_coords(coords, resolution, normalize=True, eps=0.0):
     b, _, n = coords.shape
     norm = torch.empty_like(coords)
     vox = torch.empty(b, 3, n, dtype=I32, device=coords.device)
-    call("p2pb_voxel_coords", _i(b), _i(n), _i(int(resolution)), _i(int(normalize)), _f(eps), ptr(coords), ptr(norm),
-         ptr(vox), stream_ptr())
+    call("p2pb_voxel_coords", b, n, int(resolution), int(normalize), eps, ptr(coords), ptr(norm), ptr(vox), stream_ptr())
     return norm, vox
 
 
@@ -43,9 +41,8 @@ def avg_voxelize_forward(features, coords, resolution):
     out = torch.empty(b, c, r3, dtype=F32, device=dev)
     ind = torch.empty(b, n, dtype=I32, device=dev)
     cnt = torch.empty(b, r3, dtype=I32, device=dev)
-    ws = _ws(lib().p2pb_avg_voxelize_ws_bytes(_i(b), _i(n), _i(r)), dev)
-    call("p2pb_avg_voxelize_forward", _i(b), _i(c), _i(n), _i(r), ptr(coords), ptr(features), ptr(ind), ptr(cnt),
-         ptr(out), ptr(ws), stream_ptr())
+    ws = _ws(ask("p2pb_avg_voxelize_ws_bytes", b, n, r), dev)
+    call("p2pb_avg_voxelize_forward", b, c, n, r, ptr(coords), ptr(features), ptr(ind), ptr(cnt), ptr(out), ptr(ws), stream_ptr())
     return [out, ind, cnt]
 
 
@@ -55,7 +52,7 @@ def avg_voxelize_backward(grad_y, indices, cnt):
     b, c, s = grad_y.shape
     n = indices.shape[1]
     gx = torch.empty(b, c, n, dtype=F32, device=grad_y.device)
-    call("p2pb_avg_voxelize_backward", _i(b), _i(c), _i(n), _i(s), ptr(indices), ptr(cnt), ptr(grad_y), ptr(gx),
+    call("p2pb_avg_voxelize_backward", b, c, n, s, ptr(indices), ptr(cnt), ptr(grad_y), ptr(gx),
          stream_ptr())
     return gx
 
@@ -73,7 +70,7 @@ def trilinear_devoxelize_forward(r, is_training, coords, features):
     else:
         inds = torch.zeros(1, dtype=I32, device=dev)
         wgts = torch.zeros(1, dtype=F32, device=dev)
-    call("p2pb_trilinear_devoxelize_forward", _i(b), _i(c), _i(n), _i(int(r)), _i(int(bool(is_training))), ptr(coords),
+    call("p2pb_trilinear_devoxelize_forward", b, c, n, int(r), int(bool(is_training)), ptr(coords),
          ptr(features), ptr(inds), ptr(wgts), ptr(outs), stream_ptr())
     return [outs, inds, wgts]
 
@@ -85,10 +82,10 @@ def trilinear_devoxelize_backward(grad_y, indices, weights, r):
     r3 = int(r) ** 3
     gx = torch.empty(b, c, r3, dtype=F32, device=grad_y.device)
     try:
-        call("p2pb_trilinear_devoxelize_backward", _i(b), _i(c), _i(n), _i(r3), ptr(indices), ptr(weights), ptr(grad_y),
+        call("p2pb_trilinear_devoxelize_backward", b, c, n, r3, ptr(indices), ptr(weights), ptr(grad_y),
              ptr(gx), stream_ptr())
     except P2PBError as e:
-        if not lib().p2pb_get_deterministic():
+        if not ask("p2pb_get_deterministic"):
             raise
         # (the library refuses a grid row beyond the LDS -- csrc/scatter_grad.hip SCAT_LDS_MAX, scat_rows -- in deterministic mode: only
         #  the global-atomic kernel, whose order is not fixed, would be left)
@@ -106,7 +103,7 @@ def ball_query(centers_coords, points_coords, radius, num_neighbors):
     rf = ctypes.c_float(radius).value
     r2 = ctypes.c_float(rf * rf).value  # float*float, pvcnn_ball_query.cpp:25
     idx = torch.empty(b, m, int(num_neighbors), dtype=I32, device=centers_coords.device)
-    call("p2pb_ball_query", _i(b), _i(n), _i(m), _f(r2), _i(int(num_neighbors)), ptr(centers_coords),
+    call("p2pb_ball_query", b, n, m, r2, int(num_neighbors), ptr(centers_coords),
          ptr(points_coords), ptr(idx), stream_ptr())
     return idx
 
@@ -117,7 +114,7 @@ def grouping_forward(features, indices):
     b, c, n = features.shape
     _, m, u = indices.shape
     out = torch.empty(b, c, m, u, dtype=F32, device=features.device)
-    call("p2pb_grouping_forward", _i(b), _i(c), _i(n), _i(m), _i(u), ptr(features), ptr(indices), ptr(out),
+    call("p2pb_grouping_forward", b, c, n, m, u, ptr(features), ptr(indices), ptr(out),
          stream_ptr())
     return out
 
@@ -127,7 +124,7 @@ def grouping_backward(grad_y, indices, n):
     check(grad_y, F32, "grad_y"), check(indices, I32, "indices")
     b, c, m, u = grad_y.shape
     gx = torch.empty(b, c, int(n), dtype=F32, device=grad_y.device)
-    call("p2pb_grouping_backward", _i(b), _i(c), _i(int(n)), _i(m), _i(u), ptr(grad_y), ptr(indices), ptr(gx),
+    call("p2pb_grouping_backward", b, c, int(n), m, u, ptr(grad_y), ptr(indices), ptr(gx),
          stream_ptr())
     return gx
 
@@ -151,7 +148,7 @@ def grouping_backward_pitched(grad_y, indices, n):
         return grouping_backward(grad_y.contiguous(), indices, n)
     b, c, m, u = grad_y.shape
     gx = torch.empty(b, c, int(n), dtype=F32, device=grad_y.device)
-    call("p2pb_grouping_backward_pitched", _i(b), _i(c), _i(int(n)), _i(m), _i(u), ptr(grad_y), ctypes.c_long(max(pitch, c * m * u)),
+    call("p2pb_grouping_backward_pitched", b, c, int(n), m, u, ptr(grad_y), max(pitch, c * m * u),
          ptr(indices), ptr(gx), stream_ptr())
     return gx
 
@@ -164,7 +161,7 @@ def three_nearest_neighbors_interpolate_backward_pitched(grad_y, indices, weight
         return three_nearest_neighbors_interpolate_backward(grad_y.contiguous(), indices, weights, m)
     b, c, n = grad_y.shape
     gx = torch.empty(b, c, int(m), dtype=F32, device=grad_y.device)
-    call("p2pb_three_nn_interpolate_backward_pitched", _i(b), _i(c), _i(n), _i(int(m)), ptr(grad_y), ctypes.c_long(max(pitch, c * n)),
+    call("p2pb_three_nn_interpolate_backward_pitched", b, c, n, int(m), ptr(grad_y), max(pitch, c * n),
          ptr(indices), ptr(weights), ptr(gx), stream_ptr())
     return gx
 
@@ -175,7 +172,7 @@ def gather_features_forward(features, indices):
     b, c, n = features.shape
     m = indices.shape[1]
     out = torch.empty(b, c, m, dtype=F32, device=features.device)
-    call("p2pb_gather_features_forward", _i(b), _i(c), _i(n), _i(m), ptr(features), ptr(indices), ptr(out),
+    call("p2pb_gather_features_forward", b, c, n, m, ptr(features), ptr(indices), ptr(out),
          stream_ptr())
     return out
 
@@ -185,7 +182,7 @@ def gather_features_backward(grad_y, indices, n):
     check(grad_y, F32, "grad_y"), check(indices, I32, "indices")
     b, c, m = grad_y.shape
     gx = torch.empty(b, c, int(n), dtype=F32, device=grad_y.device)
-    call("p2pb_gather_features_backward", _i(b), _i(c), _i(int(n)), _i(m), ptr(grad_y), ptr(indices), ptr(gx),
+    call("p2pb_gather_features_backward", b, c, int(n), m, ptr(grad_y), ptr(indices), ptr(gx),
          stream_ptr())
     return gx
 
@@ -205,23 +202,23 @@ def furthest_point_sampling_forward(coords, num_samples):
     if n > 16384 and m > 1 and big == "grid":
         # large clouds, pruned: one workgroup per cloud, a round revisits only the grid cells near the new sample
         # (csrc/sampling.hip fps_grid_kernel); same indices as every other FPS kernel here
-        ws = torch.empty(int(lib().p2pb_fps_grid_ws_bytes(_i(b), _i(n))), dtype=torch.uint8, device=coords.device)
-        call("p2pb_furthest_point_sampling_grid", _i(b), _i(n), _i(m), ptr(coords), ptr(ws), ptr(idx), stream_ptr())
+        ws = torch.empty(int(ask("p2pb_fps_grid_ws_bytes", b, n)), dtype=torch.uint8, device=coords.device)
+        call("p2pb_furthest_point_sampling_grid", b, n, m, ptr(coords), ptr(ws), ptr(idx), stream_ptr())
         return idx
     if 16384 < n <= 524288 and m > 1 and big != "single":
         # large clouds (BASELINE configs 4-5: 50000 points): 64 workgroups per cloud, four clouds per launch; same
         # indices as the single-workgroup kernel, 2.2x faster. A cooperative launch that loses a peer (GPU shared
         # with other work for the whole bounded spin) raises a per-cloud flag and the single-workgroup kernel
         # recomputes that cloud on the device: idx is valid either way, no host synchronisation needed.
-        ws = torch.empty(int(lib().p2pb_fps_coop_ws_bytes(_i(b), _i(n))), dtype=torch.uint8, device=coords.device)
-        rc = lib().p2pb_furthest_point_sampling_coop(_i(b), _i(n), _i(m), ptr(coords), ptr(ws), ptr(idx), stream_ptr())
+        ws = torch.empty(int(ask("p2pb_fps_coop_ws_bytes", b, n)), dtype=torch.uint8, device=coords.device)
+        rc = ask("p2pb_furthest_point_sampling_coop", b, n, m, ptr(coords), ptr(ws), ptr(idx), stream_ptr())
         if rc == 0:
             global _last_coop_flags
             _last_coop_flags = ws[b * 1024: b * 1024 + 4 * b].view(I32)  # diagnostics: fps_coop_fallbacks()
             return idx
         # (EINVAL: the device cannot hold 64 such workgroups at once -> single-workgroup kernel below)
     dist = torch.empty(b, n, dtype=F32, device=coords.device) if n > 16384 else None
-    call("p2pb_furthest_point_sampling", _i(b), _i(n), _i(m), ptr(coords), ptr(dist), ptr(idx), stream_ptr())
+    call("p2pb_furthest_point_sampling", b, n, m, ptr(coords), ptr(dist), ptr(idx), stream_ptr())
     return idx
 
 
@@ -246,7 +243,7 @@ def three_nearest_neighbors_interpolate_forward(points_coords, centers_coords, c
     idx = torch.empty(b, 3, n, dtype=I32, device=dev)
     w = torch.empty(b, 3, n, dtype=F32, device=dev)
     out = torch.empty(b, c, n, dtype=F32, device=dev)
-    call("p2pb_three_nn_interpolate_forward", _i(b), _i(c), _i(m), _i(n), ptr(points_coords), ptr(centers_coords),
+    call("p2pb_three_nn_interpolate_forward", b, c, m, n, ptr(points_coords), ptr(centers_coords),
          ptr(centers_features), ptr(idx), ptr(w), ptr(out), stream_ptr())
     return [out, idx, w]
 
@@ -256,7 +253,7 @@ def three_nearest_neighbors_interpolate_backward(grad_y, indices, weights, m):
     check(grad_y, F32, "grad_y"), check(indices, I32, "indices"), check(weights, F32, "weights")
     b, c, n = grad_y.shape
     gx = torch.empty(b, c, int(m), dtype=F32, device=grad_y.device)
-    call("p2pb_three_nn_interpolate_backward", _i(b), _i(c), _i(n), _i(int(m)), ptr(grad_y), ptr(indices),
+    call("p2pb_three_nn_interpolate_backward", b, c, n, int(m), ptr(grad_y), ptr(indices),
          ptr(weights), ptr(gx), stream_ptr())
     return gx
 
@@ -270,11 +267,10 @@ def three_nn(points_coords, centers_coords):
     w = torch.empty(b, 3, n, dtype=F32, device=points_coords.device)
     if 256 <= m and _experiment.get("nn_cells", "1") != "0":  # grid search (exact) once brute force is the slower one
         # (records in LDS up to 8192 centres, L2-resident above: PVDL's 12500-centre level)
-        ws = _ws(lib().p2pb_three_nn_cells_ws_bytes(_i(b), _i(m)), points_coords.device)
-        call("p2pb_three_nn_cells", _i(b), _i(m), _i(n), ptr(points_coords), ptr(centers_coords), ptr(idx), ptr(w),
-             ptr(ws), stream_ptr())
+        ws = _ws(ask("p2pb_three_nn_cells_ws_bytes", b, m), points_coords.device)
+        call("p2pb_three_nn_cells", b, m, n, ptr(points_coords), ptr(centers_coords), ptr(idx), ptr(w), ptr(ws), stream_ptr())
         return idx, w
-    call("p2pb_three_nn", _i(b), _i(m), _i(n), ptr(points_coords), ptr(centers_coords), ptr(idx), ptr(w), stream_ptr())
+    call("p2pb_three_nn", b, m, n, ptr(points_coords), ptr(centers_coords), ptr(idx), ptr(w), stream_ptr())
     return idx, w
 
 
@@ -284,7 +280,7 @@ def three_interpolate(centers_features, idx, w):
     b, c, m = centers_features.shape
     n = idx.shape[2]
     out = torch.empty(b, c, n, dtype=F32, device=centers_features.device)
-    call("p2pb_three_interpolate", _i(b), _i(c), _i(m), _i(n), ptr(centers_features), ptr(idx), ptr(w), ptr(out),
+    call("p2pb_three_interpolate", b, c, m, n, ptr(centers_features), ptr(idx), ptr(w), ptr(out),
          stream_ptr())
     return out
 
@@ -296,7 +292,7 @@ def group_concat(points_coords, centers_coords, points_features, indices):
     b, c, n = points_features.shape
     _, m, u = indices.shape
     out = torch.empty(b, 3 + c, m, u, dtype=F32, device=points_features.device)
-    call("p2pb_group_concat", _i(b), _i(c), _i(n), _i(m), _i(u), ptr(points_coords), ptr(centers_coords),
+    call("p2pb_group_concat", b, c, n, m, u, ptr(points_coords), ptr(centers_coords),
          ptr(points_features), ptr(indices), ptr(out), stream_ptr())
     return out
 
@@ -326,7 +322,7 @@ def ball_query_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx):
     as they are: the layer zero-fills idx first, group.py:198)"""
     b, n, m, nsample = int(b), int(n), int(m), int(nsample)
     _pn2_check((new_xyz, F32, "new_xyz", (b, m, 3)), (xyz, F32, "xyz", (b, n, 3)), (idx, I32, "idx", (b, m, nsample)))
-    call("p2pb_pn2_ball_query", _i(b), _i(n), _i(m), _f(radius), _i(nsample), ptr(new_xyz), ptr(xyz), ptr(idx), stream_ptr())
+    call("p2pb_pn2_ball_query", b, n, m, radius, nsample, ptr(new_xyz), ptr(xyz), ptr(idx), stream_ptr())
     return 1
 
 
@@ -335,7 +331,7 @@ def group_points_wrapper(b, c, n, npoints, nsample, points, idx, out):
     b, c, n, npoints, nsample = int(b), int(c), int(n), int(npoints), int(nsample)
     _pn2_check((points, F32, "points", (b, c, n)), (idx, I32, "idx", (b, npoints, nsample)),
                (out, F32, "out", (b, c, npoints, nsample)))
-    call("p2pb_grouping_forward", _i(b), _i(c), _i(n), _i(npoints), _i(nsample), ptr(points), ptr(idx), ptr(out), stream_ptr())
+    call("p2pb_grouping_forward", b, c, n, npoints, nsample, ptr(points), ptr(idx), ptr(out), stream_ptr())
     return 1
 
 
@@ -353,7 +349,7 @@ def gather_points_wrapper(b, c, n, npoints, points, idx, out):
     """PN2/sampling.cpp:16. points f32[B,C,N], idx i32[B,npoints] -> out f32[B,C,npoints]"""
     b, c, n, npoints = int(b), int(c), int(n), int(npoints)
     _pn2_check((points, F32, "points", (b, c, n)), (idx, I32, "idx", (b, npoints)), (out, F32, "out", (b, c, npoints)))
-    call("p2pb_gather_features_forward", _i(b), _i(c), _i(n), _i(npoints), ptr(points), ptr(idx), ptr(out), stream_ptr())
+    call("p2pb_gather_features_forward", b, c, n, npoints, ptr(points), ptr(idx), ptr(out), stream_ptr())
     return 1
 
 
@@ -372,7 +368,7 @@ def furthest_point_sampling_wrapper(b, n, m, points, temp, idx):
     tie order of the reference's min(2^floor(log2 N), 1024)-thread block (include/p2pb_hip.h p2pb_pn2_fps)"""
     b, n, m = int(b), int(n), int(m)
     _pn2_check((points, F32, "points", (b, n, 3)), (temp, F32, "temp", (b, n)), (idx, I32, "idx", (b, max(m, 0))))
-    call("p2pb_pn2_fps", _i(b), _i(n), _i(m), ptr(points), ptr(temp), ptr(idx), stream_ptr())
+    call("p2pb_pn2_fps", b, n, m, ptr(points), ptr(temp), ptr(idx), stream_ptr())
     return 1
 
 
@@ -381,7 +377,7 @@ def three_nn_wrapper(b, n, m, unknown, known, dist2, idx):
     b, n, m = int(b), int(n), int(m)
     _pn2_check((unknown, F32, "unknown", (b, n, 3)), (known, F32, "known", (b, m, 3)), (dist2, F32, "dist2", (b, n, 3)),
                (idx, I32, "idx", (b, n, 3)))
-    call("p2pb_pn2_three_nn", _i(b), _i(n), _i(m), ptr(unknown), ptr(known), ptr(dist2), ptr(idx), stream_ptr())
+    call("p2pb_pn2_three_nn", b, n, m, ptr(unknown), ptr(known), ptr(dist2), ptr(idx), stream_ptr())
 
 
 def three_interpolate_wrapper(b, c, m, n, points, idx, weight, out):
@@ -389,7 +385,7 @@ def three_interpolate_wrapper(b, c, m, n, points, idx, weight, out):
     b, c, m, n = int(b), int(c), int(m), int(n)
     _pn2_check((points, F32, "points", (b, c, m)), (idx, I32, "idx", (b, n, 3)), (weight, F32, "weight", (b, n, 3)),
                (out, F32, "out", (b, c, n)))
-    call("p2pb_pn2_three_interpolate", _i(b), _i(c), _i(m), _i(n), ptr(points), ptr(idx), ptr(weight), ptr(out), stream_ptr())
+    call("p2pb_pn2_three_interpolate", b, c, m, n, ptr(points), ptr(idx), ptr(weight), ptr(out), stream_ptr())
 
 
 def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_points):
@@ -398,8 +394,7 @@ def three_interpolate_grad_wrapper(b, c, n, m, grad_out, idx, weight, grad_point
     b, c, n, m = int(b), int(c), int(n), int(m)
     _pn2_check((grad_out, F32, "grad_out", (b, c, n)), (idx, I32, "idx", (b, n, 3)), (weight, F32, "weight", (b, n, 3)),
                (grad_points, F32, "grad_points", (b, c, m)))
-    if lib().p2pb_get_deterministic():
+    if ask("p2pb_get_deterministic"):
         raise P2PBError("three_interpolate_grad_wrapper: no deterministic kernel (it accumulates with fp32 atomics, whose order is "
                         "not fixed): run this backward pass outside p2p_bridge_amd.deterministic()")
-    call("p2pb_pn2_three_interpolate_grad", _i(b), _i(c), _i(n), _i(m), ptr(grad_out), ptr(idx), ptr(weight), ptr(grad_points),
-         stream_ptr())
+    call("p2pb_pn2_three_interpolate_grad", b, c, n, m, ptr(grad_out), ptr(idx), ptr(weight), ptr(grad_points), stream_ptr())

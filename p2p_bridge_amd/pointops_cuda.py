@@ -10,15 +10,13 @@ n = xyz.shape[0]). Where the reference trusts its arguments these raise RuntimeE
 wrong dtype, a non-contiguous tensor, a shape that disagrees with the integers passed, a non-zero return code.
 `ballquery_cuda` returns 1 like the reference's, the others None.
 """
-import ctypes
 import types
 
 import torch
 
-from ._lib import P2PBError, call, lib, ptr, stream_ptr
+from ._lib import P2PBError, ask, call, ptr, stream_ptr
 from .pointnet2_batch_cuda import _pn2_check, avg_voxelize_backward, avg_voxelize_forward  # noqa: F401  (PO/voxelization/vox.cu is the file already served)
 
-_i, _f = ctypes.c_int, ctypes.c_float
 F32, I32 = torch.float32, torch.int32
 
 _KNN_MAX = 100  # csrc/pointops.hip PO_KNN_MAX: the reference's per-thread arrays hold 100 entries and are overrun above
@@ -31,7 +29,7 @@ def _dim0(t, name):
 
 
 def _no_scatter_in_deterministic_mode(name):
-    if lib().p2pb_get_deterministic():
+    if ask("p2pb_get_deterministic"):
         raise P2PBError(f"{name}: no deterministic kernel (it accumulates with fp32 atomics, whose order is not fixed): run "
                         "this backward pass outside p2p_bridge_amd.deterministic()")
 
@@ -46,7 +44,7 @@ def knnquery_cuda(m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2):
                (new_offset, I32, "new_offset", (b,)), (idx, I32, "idx", (m, nsample)), (dist2, F32, "dist2", (m, nsample)))
     if not 1 <= nsample <= _KNN_MAX:
         raise RuntimeError(f"knnquery_cuda: nsample must be in [1, {_KNN_MAX}], got {nsample}")
-    call("p2pb_pointops_knnquery", _i(b), _i(n), _i(m), _i(nsample), ptr(xyz), ptr(new_xyz), ptr(offset), ptr(new_offset),
+    call("p2pb_pointops_knnquery", b, n, m, nsample, ptr(xyz), ptr(new_xyz), ptr(offset), ptr(new_offset),
          ptr(idx), ptr(dist2), stream_ptr())
 
 
@@ -57,7 +55,7 @@ def ballquery_cuda(m, radius, nsample, xyz, new_xyz, offset, new_offset, idx):
     n, b = _dim0(xyz, "xyz"), _dim0(offset, "offset")
     _pn2_check((xyz, F32, "xyz", (n, 3)), (new_xyz, F32, "new_xyz", (m, 3)), (offset, I32, "offset", (b,)),
                (new_offset, I32, "new_offset", (b,)), (idx, I32, "idx", (m, nsample)))
-    call("p2pb_pointops_ballquery", _i(b), _i(n), _i(m), _f(radius), _i(nsample), ptr(xyz), ptr(new_xyz), ptr(offset),
+    call("p2pb_pointops_ballquery", b, n, m, radius, nsample, ptr(xyz), ptr(new_xyz), ptr(offset),
          ptr(new_offset), ptr(idx), stream_ptr())
     return 1
 
@@ -71,7 +69,7 @@ def furthestsampling_cuda(b, n, xyz, offset, new_offset, tmp, idx):
         raise RuntimeError(f"idx must have one dimension, got {tuple(idx.shape)}")
     _pn2_check((xyz, F32, "xyz", (n, 3)), (offset, I32, "offset", (b,)), (new_offset, I32, "new_offset", (b,)),
                (tmp, F32, "tmp", (n,)), (idx, I32, "idx", (_dim0(idx, "idx"),)))
-    call("p2pb_pointops_furthestsampling", _i(b), _i(n), _i(idx.shape[0]), _i(n_max), ptr(xyz), ptr(offset), ptr(new_offset),
+    call("p2pb_pointops_furthestsampling", b, n, idx.shape[0], n_max, ptr(xyz), ptr(offset), ptr(new_offset),
          ptr(tmp), ptr(idx), stream_ptr())
 
 
@@ -80,7 +78,7 @@ def grouping_forward_cuda(m, nsample, c, input, idx, output):
     m, nsample, c = int(m), int(nsample), int(c)
     _pn2_check((input, F32, "input", (_dim0(input, "input"), c)), (idx, I32, "idx", (m, nsample)),
                (output, F32, "output", (m, nsample, c)))
-    call("p2pb_pointops_grouping_forward", _i(m), _i(nsample), _i(c), ptr(input), ptr(idx), ptr(output), stream_ptr())
+    call("p2pb_pointops_grouping_forward", m, nsample, c, ptr(input), ptr(idx), ptr(output), stream_ptr())
 
 
 def grouping_backward_cuda(m, nsample, c, grad_output, idx, grad_input):
@@ -91,8 +89,7 @@ def grouping_backward_cuda(m, nsample, c, grad_output, idx, grad_input):
     _pn2_check((grad_output, F32, "grad_output", (m, nsample, c)), (idx, I32, "idx", (m, nsample)),
                (grad_input, F32, "grad_input", (n, c)))
     _no_scatter_in_deterministic_mode("grouping_backward_cuda")
-    call("p2pb_pointops_grouping_backward", _i(n), _i(m), _i(nsample), _i(c), ptr(grad_output), ptr(idx), ptr(grad_input),
-         stream_ptr())
+    call("p2pb_pointops_grouping_backward", n, m, nsample, c, ptr(grad_output), ptr(idx), ptr(grad_input), stream_ptr())
 
 
 def interpolation_forward_cuda(n, c, k, input, idx, weight, output):
@@ -101,8 +98,7 @@ def interpolation_forward_cuda(n, c, k, input, idx, weight, output):
     n, c, k = int(n), int(c), int(k)
     _pn2_check((input, F32, "input", (_dim0(input, "input"), c)), (idx, I32, "idx", (n, k)), (weight, F32, "weight", (n, k)),
                (output, F32, "output", (n, c)))
-    call("p2pb_pointops_interpolation_forward", _i(n), _i(c), _i(k), ptr(input), ptr(idx), ptr(weight), ptr(output),
-         stream_ptr())
+    call("p2pb_pointops_interpolation_forward", n, c, k, ptr(input), ptr(idx), ptr(weight), ptr(output), stream_ptr())
 
 
 def interpolation_backward_cuda(n, c, k, grad_output, idx, weight, grad_input):
@@ -111,7 +107,7 @@ def interpolation_backward_cuda(n, c, k, grad_output, idx, weight, grad_input):
     _pn2_check((grad_output, F32, "grad_output", (n, c)), (idx, I32, "idx", (n, k)), (weight, F32, "weight", (n, k)),
                (grad_input, F32, "grad_input", (_dim0(grad_input, "grad_input"), c)))
     _no_scatter_in_deterministic_mode("interpolation_backward_cuda")
-    call("p2pb_pointops_interpolation_backward", _i(n), _i(c), _i(k), ptr(grad_output), ptr(idx), ptr(weight), ptr(grad_input),
+    call("p2pb_pointops_interpolation_backward", n, c, k, ptr(grad_output), ptr(idx), ptr(weight), ptr(grad_input),
          stream_ptr())
 
 
@@ -120,7 +116,7 @@ def subtraction_forward_cuda(n, nsample, c, input1, input2, idx, output):
     n, nsample, c = int(n), int(nsample), int(c)
     _pn2_check((input1, F32, "input1", (n, c)), (input2, F32, "input2", (_dim0(input2, "input2"), c)),
                (idx, I32, "idx", (n, nsample)), (output, F32, "output", (n, nsample, c)))
-    call("p2pb_pointops_subtraction_forward", _i(n), _i(nsample), _i(c), ptr(input1), ptr(input2), ptr(idx), ptr(output),
+    call("p2pb_pointops_subtraction_forward", n, nsample, c, ptr(input1), ptr(input2), ptr(idx), ptr(output),
          stream_ptr())
 
 
@@ -136,7 +132,7 @@ def subtraction_backward_cuda(n, nsample, c, idx, grad_output, grad_input1, grad
         _no_scatter_in_deterministic_mode("subtraction_backward_cuda")
     else:
         _pn2_check(*specs)
-    call("p2pb_pointops_subtraction_backward", _i(n), _i(nsample), _i(c), ptr(idx), ptr(grad_output), ptr(grad_input1),
+    call("p2pb_pointops_subtraction_backward", n, nsample, c, ptr(idx), ptr(grad_output), ptr(grad_input1),
          ptr(grad_input2), stream_ptr())
 
 
@@ -152,7 +148,7 @@ def aggregation_forward_cuda(n, nsample, c, w_c, input, position, weight, idx, o
     output f32[n,c] (the layer passes zeros); c % w_c == 0"""
     n, nsample, c, w_c = int(n), int(nsample), int(c), int(w_c)
     _pn2_check(*_aggregation_specs(n, nsample, c, w_c, input, position, weight, idx), (output, F32, "output", (n, c)))
-    call("p2pb_pointops_aggregation_forward", _i(n), _i(nsample), _i(c), _i(w_c), ptr(input), ptr(position), ptr(weight),
+    call("p2pb_pointops_aggregation_forward", n, nsample, c, w_c, ptr(input), ptr(position), ptr(weight),
          ptr(idx), ptr(output), stream_ptr())
 
 
@@ -171,7 +167,7 @@ def aggregation_backward_cuda(n, nsample, c, w_c, input, position, weight, idx, 
         _no_scatter_in_deterministic_mode("aggregation_backward_cuda")
     else:
         _pn2_check(*specs)
-    call("p2pb_pointops_aggregation_backward", _i(n), _i(nsample), _i(c), _i(w_c), ptr(input), ptr(position), ptr(weight),
+    call("p2pb_pointops_aggregation_backward", n, nsample, c, w_c, ptr(input), ptr(position), ptr(weight),
          ptr(idx), ptr(grad_output), ptr(grad_input), ptr(grad_position), ptr(grad_weight), stream_ptr())
 
 

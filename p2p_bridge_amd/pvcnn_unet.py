@@ -141,7 +141,6 @@ class _LinearAttentionCore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, heads):
         from ._lib import call, check, ptr, stream_ptr
-        import ctypes
 
         qkv = qkv.contiguous()
         check(qkv, torch.float32, "qkv")  # (raw pointers go to the kernel: device, dtype and layout are checked here)
@@ -150,8 +149,7 @@ class _LinearAttentionCore(torch.autograd.Function):
         out = torch.empty(b, heads * dh, n, dtype=qkv.dtype, device=qkv.device)
         need = ctx.needs_input_grad[0]
         ctxm = torch.empty(b, heads, dh, dh, dtype=qkv.dtype, device=qkv.device) if need else None
-        call("p2pb_linear_attention_forward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(dh), ctypes.c_int(n),
-             ptr(qkv), ptr(out), ptr(ctxm), stream_ptr())
+        call("p2pb_linear_attention_forward", b, heads, dh, n, ptr(qkv), ptr(out), ptr(ctxm), stream_ptr())
         if need:
             ctx.save_for_backward(qkv, ctxm)
             ctx.heads = heads
@@ -160,7 +158,6 @@ class _LinearAttentionCore(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         from ._lib import call, ptr, stream_ptr
-        import ctypes
 
         qkv, ctxm = ctx.saved_tensors
         b, c3, n = qkv.shape
@@ -170,8 +167,7 @@ class _LinearAttentionCore(torch.autograd.Function):
         from ._lib import check
 
         check(g, torch.float32, "grad_out")
-        call("p2pb_linear_attention_backward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(c3 // (3 * heads)),
-             ctypes.c_int(n), ptr(qkv), ptr(ctxm), ptr(g), ptr(dq), stream_ptr())
+        call("p2pb_linear_attention_backward", b, heads, c3 // (3 * heads), n, ptr(qkv), ptr(ctxm), ptr(g), ptr(dq), stream_ptr())
         return dq, None
 
 
@@ -209,7 +205,6 @@ class _SoftmaxAttentionCore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, kv, heads):
         from ._lib import call, check, ptr, stream_ptr
-        import ctypes
 
         q, kv = q.contiguous(), kv.contiguous()
         check(q, torch.float32, "q")  # (raw pointers go to the kernel: device, dtype and layout are checked here)
@@ -221,7 +216,7 @@ class _SoftmaxAttentionCore(torch.autograd.Function):
         need = any(ctx.needs_input_grad[:2])
         out = torch.empty_like(q)
         lse = torch.empty(b, heads, n, dtype=q.dtype, device=q.device) if need else None
-        call("p2pb_softmax_attention_forward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(c // heads), ctypes.c_int(n),
+        call("p2pb_softmax_attention_forward", b, heads, c // heads, n,
              ptr(q), ptr(kv), ptr(out), ptr(lse), stream_ptr())
         if need:
             ctx.save_for_backward(q, kv, out, lse)
@@ -231,7 +226,6 @@ class _SoftmaxAttentionCore(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         from ._lib import call, check, ptr, stream_ptr
-        import ctypes
 
         q, kv, out, lse = ctx.saved_tensors
         b, c, n = q.shape
@@ -239,7 +233,7 @@ class _SoftmaxAttentionCore(torch.autograd.Function):
         g = g.contiguous()
         check(g, torch.float32, "grad_out")
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        call("p2pb_softmax_attention_backward", ctypes.c_int(b), ctypes.c_int(heads), ctypes.c_int(c // heads), ctypes.c_int(n),
+        call("p2pb_softmax_attention_backward", b, heads, c // heads, n,
              ptr(q), ptr(kv), ptr(out), ptr(lse), ptr(g), ptr(dq), ptr(dkv), stream_ptr())
         return dq, dkv, None
 

@@ -17,7 +17,6 @@ the same inputs and the same numpy seed give the same bytes. Contract of the ker
 which edges are pinned to the reference by tests/golden/room_pairs.npz and which are restated: INTEGRATION.md.
 """
 import argparse
-import ctypes
 import math
 import os
 import zlib
@@ -32,7 +31,6 @@ from .evaluate_rooms import _ns, read_ply
 from .scan_fusion import _cuda
 
 F32, F64, I32, I64 = torch.float32, torch.float64, torch.int32, torch.int64
-_i = ctypes.c_int
 KNN_K = 128  # clean candidates per noisy point (utils.py:149)
 MAX_K = 128
 MAX_PATCHES = 65535  # patches of one p2pb_pairs_knn launch
@@ -48,8 +46,7 @@ def mesh_cdf(verts, faces):
         raise ValueError("mesh_cdf: empty mesh")
     area = torch.empty(faces.shape[0], dtype=F64, device=verts.device)
     bad = torch.zeros(1, dtype=I32, device=verts.device)
-    call("p2pb_pairs_tri_areas", _i(verts.shape[0]), _i(faces.shape[0]), ptr(verts), ptr(faces), ptr(area), ptr(bad),
-         stream_ptr())
+    call("p2pb_pairs_tri_areas", verts.shape[0], faces.shape[0], ptr(verts), ptr(faces), ptr(area), ptr(bad), stream_ptr())
     if int(bad.item()):
         raise ValueError(f"mesh_cdf: a face names a vertex outside [0, {verts.shape[0]})")
     return torch.cumsum(area, 0)
@@ -72,7 +69,7 @@ def sample_mesh(verts, faces, u, vcol=None, cdf=None):
     face = torch.empty(n, dtype=I32, device=dev)
     xyz = torch.empty(n, 3, dtype=F32, device=dev)
     rgb = torch.empty(n, 3, dtype=F32, device=dev) if vcol is not None else None
-    call("p2pb_pairs_sample_mesh", _i(verts.shape[0]), _i(faces.shape[0]), _i(n), ptr(verts), ptr(vcol), ptr(faces), ptr(cdf),
+    call("p2pb_pairs_sample_mesh", verts.shape[0], faces.shape[0], n, ptr(verts), ptr(vcol), ptr(faces), ptr(cdf),
          ptr(u), ptr(face), ptr(xyz), ptr(rgb), stream_ptr())
     return face, xyz, rgb
 
@@ -96,8 +93,7 @@ def patch_knn(query, ref, ref_off, K=KNN_K, return_dist=True):
         raise ValueError("patch_knn: empty batch")
     idx = torch.empty(p, s, k, dtype=I32, device=query.device)
     dist2 = torch.empty(p, s, k, dtype=F32, device=query.device) if return_dist else None
-    call("p2pb_pairs_knn", _i(p), _i(s), _i(k), _i(ref.shape[0]), ptr(query), ptr(ref), ptr(ref_off), ptr(idx), ptr(dist2),
-         stream_ptr())
+    call("p2pb_pairs_knn", p, s, k, ref.shape[0], ptr(query), ptr(ref), ptr(ref_off), ptr(idx), ptr(dist2), stream_ptr())
     return idx, dist2
 
 
@@ -114,7 +110,7 @@ def unique_assign(nn, ref_off, total=None):
     owner = torch.empty(total, dtype=I32, device=nn.device)
     assign = torch.empty(p, s, dtype=I32, device=nn.device)
     unique = torch.empty(p, dtype=I32, device=nn.device)
-    call("p2pb_pairs_unique_assign", _i(p), _i(s), _i(k), _i(total), ptr(nn), ptr(ref_off), ptr(owner), ptr(assign), ptr(unique),
+    call("p2pb_pairs_unique_assign", p, s, k, total, ptr(nn), ptr(ref_off), ptr(owner), ptr(assign), ptr(unique),
          stream_ptr())
     return assign, unique
 
@@ -134,7 +130,7 @@ def finish(noisy, noisy_rgb, ref, ref_rgb, ref_off, assign):
     noisy_out = torch.empty(p, s, 6, dtype=F32, device=dev)
     center = torch.empty(p, 3, dtype=F32, device=dev)
     scale = torch.empty(p, dtype=F32, device=dev)
-    call("p2pb_pairs_finish", _i(p), _i(s), _i(ref.shape[0]), ptr(noisy), ptr(noisy_rgb), ptr(ref), ptr(ref_rgb), ptr(ref_off),
+    call("p2pb_pairs_finish", p, s, ref.shape[0], ptr(noisy), ptr(noisy_rgb), ptr(ref), ptr(ref_rgb), ptr(ref_off),
          ptr(assign), ptr(clean_out), ptr(noisy_out), ptr(center), ptr(scale), stream_ptr())
     return clean_out, noisy_out, center, scale
 

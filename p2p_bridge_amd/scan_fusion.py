@@ -29,7 +29,7 @@ import os
 import numpy as np
 import torch
 
-from ._lib import call, lib, ptr, stream_ptr
+from ._lib import ask, call, ptr, stream_ptr
 
 F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
 SMALL_VOXEL = 64  # voxels of up to this many points: one thread per (voxel, channel); larger: chunks of a workgroup each
@@ -85,13 +85,12 @@ def backproject(image, depth, camera_to_world, intrinsic, min_depth=0.1, max_dep
     if h * w == 0:
         return torch.empty(0, 3, dtype=F32, device=dev), torch.empty(0, 3, dtype=F32, device=dev)
     valid = torch.empty(h * w, dtype=U8, device=dev)
-    call("p2pb_scan_depth_valid", ctypes.c_int(h * w), ptr(depth), ctypes.c_float(min_depth), ctypes.c_float(max_depth),
-         ptr(valid), stream_ptr())
+    call("p2pb_scan_depth_valid", h * w, ptr(depth), min_depth, max_depth, ptr(valid), stream_ptr())
     pix = torch.nonzero(valid).flatten()  # i64, ascending = row-major
     n = pix.numel()
     xyz, rgb = torch.empty(n, 3, dtype=F32, device=dev), torch.empty(n, 3, dtype=F32, device=dev)
     if n:
-        call("p2pb_scan_backproject", ctypes.c_int(n), ctypes.c_int(w), ctypes.c_int(h), ptr(pix), ptr(image), ptr(depth),
+        call("p2pb_scan_backproject", n, w, h, ptr(pix), ptr(image), ptr(depth),
              kinv.ctypes.data_as(ctypes.c_void_p), c2w.ctypes.data_as(ctypes.c_void_p), ptr(xyz), ptr(rgb), stream_ptr())
     return xyz, rgb
 
@@ -105,7 +104,7 @@ def _keys(xyz, cell, what):
     n = xyz.shape[0]
     keys = torch.empty(n, dtype=I64, device=xyz.device)
     bad = torch.zeros(1, dtype=I32, device=xyz.device)
-    call("p2pb_scan_cell_keys", ctypes.c_int(n), ptr(xyz), ctypes.c_float(cell), ptr(keys), ptr(bad), stream_ptr())
+    call("p2pb_scan_cell_keys", n, ptr(xyz), cell, ptr(keys), ptr(bad), stream_ptr())
     if int(bad.item()):
         raise ValueError(f"{what}: a coordinate is NaN or its cell index at size {cell} lies outside [-2^20, 2^20)")
     return keys, cell
@@ -143,7 +142,7 @@ def voxel_down_sample(xyz, voxel_size, *attrs):
     big = torch.nonzero(counts > SMALL_VOXEL).flatten()
     nbig = big.numel()
     if nbig:
-        rows = int(lib().p2pb_scan_big_chunk_rows())
+        rows = int(ask("p2pb_scan_big_chunk_rows"))
         per = (counts[big] + rows - 1) // rows  # chunks of each large voxel
         chunk_begin = torch.zeros(nbig + 1, dtype=I64, device=xyz.device)
         torch.cumsum(per, 0, out=chunk_begin[1:])
@@ -158,11 +157,10 @@ def voxel_down_sample(xyz, voxel_size, *attrs):
         if m * c >= 2 ** 31:
             raise ValueError(f"voxel_down_sample: {m} voxels x {c} channels is 2^31 or more")
         dst = torch.empty(m, c, dtype=F32, device=xyz.device)
-        call("p2pb_scan_segment_mean", ctypes.c_longlong(m), ctypes.c_int(c), ctypes.c_int(SMALL_VOXEL), ptr(src), ptr(perm),
-             ptr(starts), ptr(dst), stream_ptr())
+        call("p2pb_scan_segment_mean", m, c, SMALL_VOXEL, ptr(src), ptr(perm), ptr(starts), ptr(dst), stream_ptr())
         if nbig:
             partial = torch.empty(nchunks, c, dtype=F64, device=xyz.device)
-            call("p2pb_scan_segment_mean_big", ctypes.c_int(nbig), ctypes.c_int(nchunks), ctypes.c_int(c), ptr(src), ptr(perm),
+            call("p2pb_scan_segment_mean_big", nbig, nchunks, c, ptr(src), ptr(perm),
                  ptr(starts), ptr(big), ptr(chunk_begin), ptr(chunk_row0), ptr(chunk_rows), ptr(partial), ptr(dst), stream_ptr())
         out.append(dst)
     return tuple(out)
@@ -187,8 +185,8 @@ def remove_radius_outliers(xyz, nb_points, search_radius, include_self=True):
     reach = np.nextafter(np.float32(math.sqrt(float(r2)) * (1.0 + 1e-6)), np.float32(np.inf))
     pts, skeys, perm, cell = _grid(xyz, r, "remove_radius_outliers")
     counts = torch.empty(n, dtype=I32, device=dev)
-    call("p2pb_scan_radius_count", ctypes.c_int(n), ctypes.c_int(n), ptr(pts), ptr(pts), ptr(skeys), ctypes.c_float(cell),
-         ctypes.c_float(float(r2)), ctypes.c_float(float(reach)), ctypes.c_int(min(need, 2 ** 31 - 1)), ptr(counts), stream_ptr())
+    call("p2pb_scan_radius_count", n, n, ptr(pts), ptr(pts), ptr(skeys), cell,
+         float(r2), float(reach), min(need, 2 ** 31 - 1), ptr(counts), stream_ptr())
     mask = torch.empty(n, dtype=torch.bool, device=dev)
     mask[perm] = counts >= need  # (the queries ran in sorted order: neighbouring threads read the same cells)
     return mask
@@ -245,19 +243,19 @@ def knn_kth_distance(query, ref, k):
             break
         cell = max(cell * step, floor)
     unresolved = torch.empty(nq, dtype=U8, device=dev)
-    call("p2pb_scan_knn_grid", ctypes.c_int(nq), ctypes.c_int(n), ctypes.c_int(k), ctypes.c_int(KNN_RINGS), None, ptr(query),
-         ptr(pts), ptr(skeys), ctypes.c_float(cell), ptr(out), ptr(unresolved), stream_ptr())
+    call("p2pb_scan_knn_grid", nq, n, k, KNN_RINGS, None, ptr(query),
+         ptr(pts), ptr(skeys), cell, ptr(out), ptr(unresolved), stream_ptr())
     left = torch.nonzero(unresolved).flatten().to(I32)
     level = 1
     while left.numel():
         if level >= KNN_LEVELS or left.numel() * n <= KNN_BRUTE_PAIRS:
-            call("p2pb_scan_knn_brute", ctypes.c_int(left.numel()), ctypes.c_int(n), ctypes.c_int(k), ptr(left), ptr(query),
+            call("p2pb_scan_knn_brute", left.numel(), n, k, ptr(left), ptr(query),
                  ptr(ref), ptr(out), stream_ptr())
             break
         level += 1
         pts, skeys, _, cell = _grid(ref, cell * 4.0, "knn_kth_distance")
-        call("p2pb_scan_knn_grid", ctypes.c_int(left.numel()), ctypes.c_int(n), ctypes.c_int(k), ctypes.c_int(KNN_RINGS),
-             ptr(left), ptr(query), ptr(pts), ptr(skeys), ctypes.c_float(cell), ptr(out), ptr(unresolved), stream_ptr())
+        call("p2pb_scan_knn_grid", left.numel(), n, k, KNN_RINGS,
+             ptr(left), ptr(query), ptr(pts), ptr(skeys), cell, ptr(out), ptr(unresolved), stream_ptr())
         left = left[unresolved[left.long()] != 0].contiguous()
     return out
 

@@ -29,6 +29,93 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().p2pb_target_arch() == b"gfx950"
 
 
+def test_binding_types_every_declared_symbol_from_the_header():
+    """_lib parses the header into the table lib() types the library with: the same names as the independent regex above, and
+    every one of them carries its restype and argtypes on the loaded library"""
+    from p2p_bridge_amd import _lib, build
+
+    build.build()
+    syms = header_symbols()
+    table, version = _lib.parse_header(open(HDR).read())
+    assert sorted(table) == syms == sorted(_lib.SIGNATURES) and version == _lib.ABI_VERSION
+    lib = _lib.lib()
+    for s in syms:
+        fn = getattr(lib, s)
+        assert fn.argtypes is not None and list(fn.argtypes) == table[s][1] and fn.restype is table[s][0], s
+
+
+def test_binding_types_match_hand_written_anchors():
+    """signatures written out here from the header's text, not derived through the parser"""
+    from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_longlong, c_size_t, c_void_p
+
+    from p2p_bridge_amd import _lib
+
+    lib = _lib.lib()
+    assert lib.p2pb_knn_points_ws_bytes.restype is c_size_t and list(lib.p2pb_knn_points_ws_bytes.argtypes) == [c_int] * 3
+    assert lib.p2pb_target_arch.restype is c_char_p and list(lib.p2pb_target_arch.argtypes) == []
+    a = lib.p2pb_linear_rows.argtypes
+    assert len(a) == 11 and all(a[i] is c_long for i in (4, 6, 9)) and all(a[i] is c_void_p for i in (3, 5, 7, 8, 10))
+    assert all(a[i] is c_int for i in (0, 1, 2)) and lib.p2pb_linear_rows.restype is c_int
+    assert lib.p2pb_voxel_coords.argtypes[4] is c_float
+    assert all(lib.p2pb_optim_clip_adam_step.argtypes[i] is c_double for i in range(5, 10))
+    assert lib.p2pb_optim_clip_adam_step.argtypes[4] is c_void_p and lib.p2pb_optim_clip_adam_step.argtypes[10] is c_int
+    assert lib.p2pb_row_max_forward.argtypes[0] is c_long
+    assert lib.p2pb_pairwise_emd.argtypes[8] is c_size_t
+    assert lib.p2pb_debug_pointwise_form.argtypes[3] is c_void_p
+    assert lib.p2pb_scan_segment_mean.argtypes[0] is c_longlong
+
+
+def test_binding_refuses_a_wrong_argument_count():
+    """ctypes itself passes surplus arguments of a cdecl function on silently: call() and ask() compare the count first
+    (host-state entry points only: nothing is launched)"""
+    from p2p_bridge_amd import _lib
+
+    base = _lib.ask("p2pb_get_split_terms")
+    with pytest.raises(_lib.P2PBError, match=r"p2pb_set_split_terms_thread takes 1 .* called with 2"):
+        _lib.call("p2pb_set_split_terms_thread", 0, 0)
+    with pytest.raises(_lib.P2PBError, match=r"p2pb_set_split_terms_thread takes 1 .* called with 0"):
+        _lib.call("p2pb_set_split_terms_thread")
+    with pytest.raises(_lib.P2PBError, match=r"p2pb_conv3d_k3_stats_floats takes 3 .* called with 2"):
+        _lib.ask("p2pb_conv3d_k3_stats_floats", 1, 8)
+    with pytest.raises(_lib.P2PBError, match=r"p2pb_conv3d_k3_stats_floats takes 3 .* called with 4"):
+        _lib.ask("p2pb_conv3d_k3_stats_floats", 1, 8, 8, 8)
+    assert _lib.call("p2pb_set_split_terms_thread", 0) is None
+    assert _lib.ask("p2pb_conv3d_k3_stats_floats", 1, 8, 8) > 0
+    assert _lib.ask("p2pb_get_split_terms") == base
+
+
+def test_binding_refuses_a_wrong_argument_type():
+    """a float for an int parameter, a C int for a long long one (host-only entry points; the conversion fails before the call)"""
+    from p2p_bridge_amd import _lib
+
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.ask("p2pb_conv3d_k3_stats_floats", 1.5, 8, 8)
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.call("p2pb_set_split_terms_thread", 1.5)
+    with pytest.raises(ctypes.ArgumentError):
+        _lib.ask("p2pb_room_fps_jobs_ws_bytes", ctypes.c_int(7))
+    assert _lib.ask("p2pb_room_fps_jobs_ws_bytes", 7) == _lib.ask("p2pb_room_fps_jobs_ws_bytes", ctypes.c_longlong(7))
+    assert _lib.ask("p2pb_room_fps_jobs_ws_bytes", 2 ** 33) == 16 * 2 ** 33  # (neither narrowed to a C int on the way in nor out)
+
+
+def test_parser_refuses_a_header_it_cannot_type():
+    from p2p_bridge_amd import _lib
+
+    text = open(HDR).read()
+    good = "int p2pb_voxel_coords(int b, int n, int r, int normalize, float eps,"
+    assert text.count(good) == 1
+    for bad in (good.replace("float eps", "half eps"), good.replace("float eps", "float"), good.replace("int p2pb", "status_t p2pb"),
+                good.replace("int r,", "int r[3],")):
+        with pytest.raises(_lib.P2PBError, match="p2pb_voxel_coords"):
+            _lib.parse_header(text.replace(good, bad))
+    with pytest.raises(_lib.P2PBError, match="p2pb_x"):
+        _lib.parse_header(text.replace(good, "#define P2PB_X(a) p2pb_x(a)\n" + good) + "\nstatic inline int f(void) { return p2pb_x(1); }\n")
+    with pytest.raises(_lib.P2PBError, match="p2pb_voxel_coords"):
+        _lib.parse_header(text + "\nint p2pb_voxel_coords(int b);\n")  # declared twice
+    with pytest.raises(_lib.P2PBError, match="P2PB_ABI_VERSION"):
+        _lib.parse_header(text.replace("#define P2PB_ABI_VERSION", "#define P2PB_ABI_VERSION_"))
+
+
 def test_library_contains_gfx950_code_object():
     from p2p_bridge_amd import _lib
 

@@ -183,7 +183,7 @@ def compute_three_interp_add():
 
 
 def compute_devox():
-    from p2p_bridge_amd.fused import _i, call, ptr, stream_ptr
+    from p2p_bridge_amd.fused import call, ptr, stream_ptr
 
     out = {}
     for r in DV_R:
@@ -194,7 +194,7 @@ def compute_devox():
                     for use_add in (0, 1):
                         y = torch.empty(DV_B, c, n, dtype=torch.float32, device="cuda")
                         # (the entry point itself: fused.devoxelize_affine always passes the affine)
-                        call("p2pb_trilinear_devoxelize_cl_affine", _i(DV_B), _i(c), _i(n), _i(r), ptr(co), ptr(grid),
+                        call("p2pb_trilinear_devoxelize_cl_affine", DV_B, c, n, r, ptr(co), ptr(grid),
                              ptr(a if use_aff else None), ptr(bb if use_aff else None), ptr(h if use_add else None),
                              ptr(hs if use_add else None), ptr(hb if use_add else None), ptr(y), stream_ptr())
                         out[f"devox/r{r}_n{n}_c{c}_aff{use_aff}_add{use_add}/out"] = _digest(y)

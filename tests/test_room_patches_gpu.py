@@ -193,7 +193,7 @@ def test_fps_jobs_inside_a_poisoned_arena(R, arena, lengths, m):
     made = [(r["dtype"], r["shape"]) for r in arena.records[n0:]]
     assert (torch.int32, (len(jo), m)) in made
     streamed = sum(L for L in jl if L > R.FPS_JOB_TIERS[-1])
-    ws_floats = int(R.lib().p2pb_room_fps_jobs_ws_bytes(R._ll(streamed))) // 4
+    ws_floats = int(R.lib().p2pb_room_fps_jobs_ws_bytes(streamed)) // 4
     assert ws_floats >= 4 * streamed and ((torch.float32, (ws_floats,)) in made) == (streamed > 0)
     for j, (o, L, s) in enumerate(zip(jo, jl, js)):
         eq(got[j].long(), oracle_job(pts, idx[o:o + L], s, m), f"job {j} (list of {L}, start {s})")
