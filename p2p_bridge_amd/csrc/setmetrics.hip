@@ -10,11 +10,11 @@
 // fma(dz, dz, fma(dy, dy, dx * dx)) on t - q) without the index bookkeeping. The minima are summed in fp64 in a fixed order
 // (thread-sequential, then an LDS tree): no floating-point atomics, same bits every run.
 //
-// EMD (em_*_kernel): approxmatch (emd.hip) only ever adds into match[l, k] and never reads it, and matchcost is linear in it, so
-// cost = sum_levels sum_kl w_kl d_kl is accumulated level by level per point k and the n x m match matrix (16 MB per pair at
-// 2048 points, read and written at each of the 10 levels) is never stored. Same per-level arithmetic as emd.hip's single-pass
-// kernels. Pairs are processed in chunks bounded by the caller's workspace.
-#include "common.h"
+// EMD: approxmatch only ever adds into match[l, k] and never reads it, and matchcost is linear in it, so
+// cost = sum_levels sum_kl w_kl d_kl is accumulated level by level per point k and the n x m match matrix is never stored:
+// the single-pass kernels of emd_sweep.h, which emd.hip runs too, with the pair (i, j) as their addressing. Pairs are
+// processed in chunks bounded by the caller's workspace.
+#include "emd_sweep.h"
 
 typedef float smf2 __attribute__((ext_vector_type(2)));
 
@@ -123,130 +123,14 @@ extern "C" int p2pb_pairwise_chamfer(int s, int r, int n, int m, const float *A,
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// approximate EMD for a chunk of pairs. Pair p = p0 + blockIdx.y -> (i, j) = (p / r, p % r). Work arrays of one pair:
-//   remainL[n] | ratioL[n] | costk[n] | remainR[m] | ratioR[m]
+// approximate EMD for a chunk of pairs: emd_sweep.h on EmdPairwise's work arrays, then the mean of costk
 // ------------------------------------------------------------------------------------------------------------------
-#define EM_TILE 1024
 #define EM_PAIRS_MAX 32768
 
-struct EmPair {
-  const float *xyz1, *xyz2;
-  float *remainL, *ratioL, *costk, *remainR, *ratioR;
-};
-__device__ __forceinline__ EmPair em_pair(int p0, int r, int n, int m, const float *A, const float *B, float *ws) {
-  const int p = p0 + blockIdx.y;
-  EmPair e;
-  e.xyz1 = A + (size_t)(p / r) * n * 3;
-  e.xyz2 = B + (size_t)(p % r) * m * 3;
-  e.remainL = ws + (size_t)blockIdx.y * (3 * (size_t)n + 2 * (size_t)m);
-  e.ratioL = e.remainL + n, e.costk = e.ratioL + n, e.remainR = e.costk + n, e.ratioR = e.remainR + m;
-  return e;
-}
-
-__global__ __launch_bounds__(256) void em_init_kernel(int p0, int r, int n, int m, float multiL, float multiR, float *ws) {
-  const EmPair e = em_pair(p0, r, n, m, nullptr, nullptr, ws);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) e.remainL[i] = multiL, e.costk[i] = 0.0f;
-  if (i < m) e.remainR[i] = multiR;
-}
-
-// ratioL_k = remainL_k / (1e-9 + sum_l exp(level d_kl) remainR_l)                      (emd.hip am_ratio_l_kernel)
-__global__ __launch_bounds__(256) void em_ratio_l_kernel(int p0, int r, int n, int m, float level,
-                                                         const float *__restrict__ A, const float *__restrict__ B,
-                                                         float *ws) {
-  __shared__ float4 buf[EM_TILE];
-  const EmPair e = em_pair(p0, r, n, m, A, B, ws);
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  const bool ok = k < n;
-  const float *p = e.xyz1 + (size_t)(ok ? k : 0) * 3;
-  const float x1 = p[0], y1 = p[1], z1 = p[2];
-  float suml = 1e-9f;
-  for (int l0 = 0; l0 < m; l0 += EM_TILE) {
-    const int ln = min(EM_TILE, m - l0);
-    __syncthreads();
-    for (int l = threadIdx.x; l < ln; l += 256) {
-      const float *q = e.xyz2 + (size_t)(l0 + l) * 3;
-      buf[l] = make_float4(q[0], q[1], q[2], e.remainR[l0 + l]);
-    }
-    __syncthreads();
-    for (int l = 0; l < ln; ++l) {
-      const float4 t = buf[l];
-      suml += __expf(level * sqdist3(t.x - x1, t.y - y1, t.z - z1)) * t.w;
-    }
-  }
-  if (ok) e.ratioL[k] = __fdiv_rn(e.remainL[k], suml);
-}
-
-// sumr_l = remainR_l sum_k exp(level d_kl) ratioL_k; consumption; ratioR; remainR update   (emd.hip am_ratio_r_kernel)
-__global__ __launch_bounds__(256) void em_ratio_r_kernel(int p0, int r, int n, int m, float level,
-                                                         const float *__restrict__ A, const float *__restrict__ B,
-                                                         float *ws) {
-  __shared__ float4 buf[EM_TILE];
-  const EmPair e = em_pair(p0, r, n, m, A, B, ws);
-  const int l = blockIdx.x * 256 + threadIdx.x;
-  const bool ok = l < m;
-  const float *q = e.xyz2 + (size_t)(ok ? l : 0) * 3;
-  const float x2 = q[0], y2 = q[1], z2 = q[2];
-  float sumr = 0.0f;
-  for (int k0 = 0; k0 < n; k0 += EM_TILE) {
-    const int kn = min(EM_TILE, n - k0);
-    __syncthreads();
-    for (int k = threadIdx.x; k < kn; k += 256) {
-      const float *p = e.xyz1 + (size_t)(k0 + k) * 3;
-      buf[k] = make_float4(p[0], p[1], p[2], e.ratioL[k0 + k]);
-    }
-    __syncthreads();
-    for (int k = 0; k < kn; ++k) {
-      const float4 t = buf[k];
-      sumr += __expf(level * sqdist3(x2 - t.x, y2 - t.y, z2 - t.z)) * t.w;
-    }
-  }
-  if (!ok) return;
-  const float rr = e.remainR[l];
-  sumr *= rr;
-  const float consumption = fminf(__fdiv_rn(rr, sumr + 1e-9f), 1.0f);
-  e.ratioR[l] = consumption * rr;
-  e.remainR[l] = fmaxf(0.0f, rr - sumr);
-}
-
-// w_kl = exp(level d_kl) ratioL_k ratioR_l is what approxmatch adds to match[l, k]; here it goes straight into
-// remainL_k -= sum_l w_kl and costk_k += sum_l d_kl w_kl                       (emd.hip am_match_kernel + matchcost_kernel)
-__global__ __launch_bounds__(256) void em_match_cost_kernel(int p0, int r, int n, int m, float level,
-                                                            const float *__restrict__ A, const float *__restrict__ B,
-                                                            float *ws) {
-  __shared__ float4 buf[EM_TILE];
-  const EmPair e = em_pair(p0, r, n, m, A, B, ws);
-  const int k = blockIdx.x * 256 + threadIdx.x;
-  const bool ok = k < n;
-  const float *p = e.xyz1 + (size_t)(ok ? k : 0) * 3;
-  const float x1 = p[0], y1 = p[1], z1 = p[2];
-  const float rl = ok ? e.ratioL[k] : 0.0f;
-  float suml = 0.0f, cst = 0.0f;
-  for (int l0 = 0; l0 < m; l0 += EM_TILE) {
-    const int ln = min(EM_TILE, m - l0);
-    __syncthreads();
-    for (int l = threadIdx.x; l < ln; l += 256) {
-      const float *q = e.xyz2 + (size_t)(l0 + l) * 3;
-      buf[l] = make_float4(q[0], q[1], q[2], e.ratioR[l0 + l]);
-    }
-    __syncthreads();
-    for (int l = 0; l < ln; ++l) {
-      const float4 t = buf[l];
-      const float d = sqdist3(t.x - x1, t.y - y1, t.z - z1);
-      const float w = __expf(level * d) * rl * t.w;
-      suml += w;
-      cst += d * w;
-    }
-  }
-  if (!ok) return;
-  e.remainL[k] = fmaxf(0.0f, e.remainL[k] - suml);
-  e.costk[k] += cst;
-}
-
 // out[p] = fp32(sum_k costk_k / n): fp64, thread-sequential then an LDS tree (fixed order)
-__global__ __launch_bounds__(256) void em_finish_kernel(int p0, int r, int n, int m, float *ws, float *__restrict__ out) {
+__global__ __launch_bounds__(256) void em_finish_kernel(EmdPairwise addr, int n, int m, float *__restrict__ out) {
   __shared__ double red[256];
-  const EmPair e = em_pair(p0, r, n, m, nullptr, nullptr, ws);
+  const EmdProblem e = addr(blockIdx.y, n, m);
   double acc = 0.0;
   for (int k = threadIdx.x; k < n; k += 256) acc += (double)e.costk[k];
   red[threadIdx.x] = acc;
@@ -255,7 +139,7 @@ __global__ __launch_bounds__(256) void em_finish_kernel(int p0, int r, int n, in
     if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[p0 + blockIdx.y] = (float)(red[0] / (double)n);
+  if (threadIdx.x == 0) out[addr.p0 + blockIdx.y] = (float)(red[0] / (double)n);
 }
 
 static size_t em_pair_bytes(int n, int m) { return (3 * (size_t)n + 2 * (size_t)m) * sizeof(float); }
@@ -274,18 +158,11 @@ extern "C" int p2pb_pairwise_emd(int s, int r, int n, int m, const float *A, con
   hipStream_t st = (hipStream_t)stream;
   const long pairs = (long)s * r;
   const long chunk = (long)(fit < EM_PAIRS_MAX ? fit : EM_PAIRS_MAX);
-  const float multiL = n >= m ? 1.0f : (float)(m / n), multiR = n >= m ? (float)(n / m) : 1.0f;  // emd_kernel.cu:46-52
-  float *w = (float *)ws;
   for (long p0 = 0; p0 < pairs; p0 += chunk) {
     const unsigned np = (unsigned)(pairs - p0 < chunk ? pairs - p0 : chunk);
-    hipLaunchKernelGGL(em_init_kernel, dim3(cdiv(n > m ? n : m, 256), np), dim3(256), 0, st, (int)p0, r, n, m, multiL, multiR, w);
-    for (int lv = 7; lv >= -2; --lv) {
-      const float level = lv == -2 ? 0.0f : -powf(4.0f, (float)lv);
-      hipLaunchKernelGGL(em_ratio_l_kernel, dim3(cdiv(n, 256), np), dim3(256), 0, st, (int)p0, r, n, m, level, A, B, w);
-      hipLaunchKernelGGL(em_ratio_r_kernel, dim3(cdiv(m, 256), np), dim3(256), 0, st, (int)p0, r, n, m, level, A, B, w);
-      hipLaunchKernelGGL(em_match_cost_kernel, dim3(cdiv(n, 256), np), dim3(256), 0, st, (int)p0, r, n, m, level, A, B, w);
-    }
-    hipLaunchKernelGGL(em_finish_kernel, dim3(1, np), dim3(256), 0, st, (int)p0, r, n, m, w, out);
+    const EmdPairwise addr = {A, B, (float *)ws, (int)p0, r};
+    emd_anneal(addr, (int)np, n, m, 1, st);
+    hipLaunchKernelGGL(em_finish_kernel, dim3(1, np), dim3(256), 0, st, addr, n, m, out);
   }
   return p2pb_launch_status();
 }

@@ -26,11 +26,12 @@ relative and backward / max |grad| on the own match):
 The two matchcost kernels sum in fp32 where the oracle sums in double, hence ratios up to 11 there, all under the 1e-6 floor.
 The last row is what these tests changed: with whole-tile chunks the 1024 sources were never split while the 4096 targets were
 split in 4, and the kernel stood at cost 1.3e-6 (15 x the oracle) and per-target sums 4.7e-5 (34 x) -- see am_chunk_len in
-csrc/emd.hip. pairwise_emd: 8.4e-7 / 7.2e-7 at 256 x 256, 1.0e-6 / 2.9e-6 at 256 x 128. Auction: at every case and hand-over
+csrc/emd_sweep.h. pairwise_emd: 8.4e-7 / 7.2e-7 at 256 x 256, 1.0e-6 / 2.9e-6 at 256 x 128. Auction: at every case and hand-over
 round the kernels show the C oracle's own figures to all printed digits (slack - eps 1.2e-7 .. 2.3e-7, cost - optimum 0 ..
 8.2e-3 against n eps = 0.128 .. 2.56); train.make_align_fn returns the Hungarian permutation.
 
-Not guarded here: the start value of `sumr` in am_ratio_r_fin_kernel. Starting it at 1e-9f instead of 0 passes every test of
+Not guarded here: the start value of the finisher of the chunked ratio-R sums (EmdRatioR::kStart in csrc/emd_sweep.h, which
+emd_finish_kernel starts from). Starting it at 1e-9f instead of 0 passes every test of
 this file: 1e-9 is below half an ulp of any partial sum above 0.03, and where the partials vanish the consumption clamps to 1
 and rr - 1e-9 rr == rr, so at these sizes the result does not change by a bit. That line is guarded by
 tests/test_ops_parity_gpu.py::test_approxmatch_chunked_equals_single_pass, which sees the change at 1 x 4096 x 4096 (1.4e-4
@@ -94,6 +95,25 @@ def test_auction_slackness_and_optimality(met, name, persist_from, monkeypatch):
     assert (rep.cost >= rep.opt - 1e-9).all() and (rep.cost <= rep.opt + case.n * (case.eps + SLACK_MARGIN)).all()
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs a second GPU")
+def test_auction_persistent_tail_on_second_device(met, monkeypatch):
+    """One process, the auction on device 0 and then on device 1 at 1 x 4096: the persistent tail needs 18 * 4096 = 73,728 B
+    of LDS, above the 64 KB a kernel gets without opting in, and the opt-in holds per device. A launcher that opts in once per
+    process has the second launch refused (rc 0). The cloud is a shuffled copy under noise 0.012: the C oracle is one-to-one
+    after round 11 and before round 14, so the tail (from round 10) still moves objects and 30 rounds leave a margin."""
+    monkeypatch.delenv("P2PB_EXPERIMENT", raising=False)
+    n = 4096
+    g = torch.Generator().manual_seed(0)
+    x2 = torch.rand(1, n, 3, generator=g)
+    x1 = (x2[:, torch.randperm(n, generator=g)] + 0.012 * torch.randn(1, n, 3, generator=g)).contiguous()
+    for dev in ("cuda:0", "cuda:1"):
+        with torch.cuda.device(dev):
+            rc, _, a, inv, _ = C.run_auction(met.emd_assignment, x1, x2, 0.01, 30, dev)
+        assert rc == 1, dev
+        assert torch.equal(a.long().sort(1).values, torch.arange(n).expand_as(a)), dev
+        assert torch.equal(torch.gather(inv.long(), 1, a.long()), torch.arange(n).expand_as(a)), dev
+
+
 def test_align_fn_returns_the_hungarian_permutation(monkeypatch):
     """train.make_align_fn (eps 0.01, 100 rounds, [B,3,N] layout) on the shuffled noisy copies: the C oracle reaches the
     optimum itself there (tests/test_emd_check.py), so the aligned clean patch is the Hungarian permutation of the clean
@@ -131,7 +151,7 @@ def test_approxmatch_and_matchcost_against_float64(met, case):
     b, n, m = case.b, case.n, case.m
     chunks = {(1, 2048, 2048): 2, (1, 1024, 4096): 4}.get((b, n, m), 1)
     temp = int(lib().p2pb_approxmatch_temp_floats(b, n, m))
-    assert temp == 2 * (n + m) * b + (chunks * b * max(n, m) if chunks > 1 else 0)  # (the chunked launches: PART + *_fin)
+    assert temp == 2 * (n + m) * b + (chunks * b * max(n, m) if chunks > 1 else 0)  # (the chunked launches: PART + finisher)
     x1, x2, gc, ref, eo = approx_reference(case)
     eh, match = C.approx_errors(met.emd_cuda, x1, x2, gc, ref, "cuda")
     print(f"\n{case}\n  oracle - fp64 {eo}\n  hip    - fp64 {eh}\n  ratios " +

@@ -216,7 +216,7 @@ def test_emd_known_answer_and_parity(met, golden_dir):
 
 
 def test_approxmatch_chunked_equals_single_pass(tmp_path):
-    """small batches split the inner cloud over blockIdx.y and add the partial sums in chunk order (csrc/emd.hip): same
+    """small batches split the inner cloud over blockIdx.y and add the partial sums in chunk order (csrc/emd_sweep.h): same
     match matrix as the single-pass kernels (P2PB_EXPERIMENT am_chunks=1) up to the summation order -- checked at sizes where
     approxmatch itself is too ill-conditioned (n != m, 4096^2) for a 2e-3 comparison with the expf-based oracle"""
     import subprocess
