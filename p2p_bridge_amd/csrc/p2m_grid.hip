@@ -11,35 +11,14 @@
 // fp32 closest point; c < 1 because the unit normal is n / (|n| + 1e-8). Triangles without such a finite box are tested
 // against everything. (3) The minimum is lexicographic in (distance, index) and the stopping test is STRICT, so the lowest
 // index among equal distances wins whatever the visiting order and however often a triangle is met.
-// The grid is sorted cell keys (scan.hip's idiom and key format): the cells (x, y, z0..z1) of one column are one run.
+// The grid is cell_grid.h's sorted cell keys, the one scan.hip searches: the points' keys come from p2pb_scan_cell_keys.
 #include "common.h"
 
+#include "cell_grid.h"
 #include "p2m_geom.h"
 
-#define PG_KEY_HALF 1048576  // p2pb_scan_cell_keys' range: cell indices in [-2^20, 2^20)
 #define PG_MAX_RING 8
 #define PG_PAD_SCALE 1.9073486e-6f  // 2^-19: pad = mag * 2^-19 >= 16 ulp of any coordinate within mag
-
-// ---- cells (the definitions of scan.hip's scan_cell / scan_key: the points' keys come from p2pb_scan_cell_keys) ---------
-__device__ __forceinline__ int pg_cell(float p, float cell, bool *ok) {
-  const float q = floorf(__fdiv_rn(p, cell));
-  *ok = q >= -(float)PG_KEY_HALF && q < (float)PG_KEY_HALF;
-  return *ok ? (int)q : 0;
-}
-
-__device__ __forceinline__ long long pg_key(int kx, int ky, int kz) {
-  return ((long long)(kx + PG_KEY_HALF) << 42) | ((long long)(ky + PG_KEY_HALF) << 21) | (long long)(kz + PG_KEY_HALF);
-}
-
-// first index in the ascending keys[lo..n) whose key is >= key
-__device__ __forceinline__ int pg_lower_bound(const long long *__restrict__ keys, int lo, int n, long long key) {
-  int hi = n;
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ V3 load3(const float *__restrict__ p) { return {p[0], p[1], p[2]}; }
 
@@ -51,10 +30,10 @@ __device__ __forceinline__ void pg_take(float &best, int &bi, float d, int i) {
   }
 }
 
-// every unvisited box / point lies at least this far away after ring rho around cells of magnitude <= cmax: rho cell edges,
-// less the rounding of the two fp32 quotients (2^-23 of the cell indices, as in scan.hip), less the pad, times the factor c
+// every unvisited box / point lies at least this far away after ring rho around cells of magnitude <= cmax: the grid's ring
+// bound, less the pad, times the factor c
 __device__ __forceinline__ float pg_reach(int rho, float cmax, float cell, float pad, float shrink) {
-  return ((((float)rho - 1.1920929e-7f * (cmax + (float)rho + 2.0f)) * cell) * 0.999999f - pad) * shrink;
+  return (cell_ring_bound(rho, cmax, cell) - pad) * shrink;
 }
 
 // strict: an unvisited candidate AT the bound may tie with the best and carry a lower index. reach > 1e-15 keeps its
@@ -127,8 +106,8 @@ __device__ __forceinline__ bool pg_box_cells(const float *__restrict__ b, float 
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     bool o0, o1;
-    lo[a] = pg_cell(b[a], cell, &o0);
-    hi[a] = pg_cell(b[3 + a], cell, &o1);
+    lo[a] = cell_of(b[a], cell, &o0);
+    hi[a] = cell_of(b[3 + a], cell, &o1);
     ok = ok && o0 && o1 && lo[a] <= hi[a];
   }
   return ok;
@@ -167,10 +146,31 @@ __global__ __launch_bounds__(256) void pg_fill_kernel(int nt, const int *__restr
     for (int y = lo[1]; y <= hi[1]; ++y)
       for (int z = lo[2]; z <= hi[2]; ++z) {
         if (w < 0 || w >= end || w >= total) return;  // never leaves the triangle's own slots, whatever counts says
-        keys[w] = pg_key(x, y, z);
+        keys[w] = cell_key(x, y, z);
         ids[w] = t;
         ++w;
       }
+}
+
+// ---- the ring walk -------------------------------------------------------------------------------------------------------
+// Ring rho around the cell box [lo, hi] (a point: lo == hi) is the box grown by rho cells on every side. visit(s, e) is
+// called for each run [s, e) of the sorted keys[0..n) that ring rho ADDS to the cube of ring rho - 1, which has been searched:
+// a whole column on the rim, of an inner column only the two end cells. Cells beyond the key range hold nothing.
+template <class Visit>
+__device__ __forceinline__ void pg_ring_runs(const long long *__restrict__ keys, int n, const int (&lo)[3], const int (&hi)[3],
+                                             int rho, Visit visit) {
+  const int z0 = max(lo[2] - rho, -CELL_KEY_HALF), z1 = min(hi[2] + rho, CELL_KEY_HALF - 1);
+  for (int x = max(lo[0] - rho, -CELL_KEY_HALF); x <= min(hi[0] + rho, CELL_KEY_HALF - 1); ++x)
+    for (int y = max(lo[1] - rho, -CELL_KEY_HALF); y <= min(hi[1] + rho, CELL_KEY_HALF - 1); ++y) {
+      const bool inner = rho > 1 && x > lo[0] - rho && x < hi[0] + rho && y > lo[1] - rho && y < hi[1] + rho;
+      for (int part = 0; part < (inner ? 2 : 1); ++part) {
+        const int za = inner ? (part ? hi[2] + rho : lo[2] - rho) : z0, zb = inner ? za : z1;
+        if (za < -CELL_KEY_HALF || zb >= CELL_KEY_HALF) continue;
+        int s, e;
+        cell_column(keys, n, x, y, za, zb, s, e);
+        visit(s, e);
+      }
+    }
 }
 
 // ---- point -> face -------------------------------------------------------------------------------------------------------
@@ -184,40 +184,25 @@ __global__ __launch_bounds__(256) void pg_point_face_kernel(int np, int nt, int 
   if (i >= np) return;
   const V3 p = load3(pts + (size_t)i * 3);
   bool okx, oky, okz;
-  const int cx = pg_cell(p.x, cell, &okx), cy = pg_cell(p.y, cell, &oky), cz = pg_cell(p.z, cell, &okz);
+  const int c[3] = {cell_of(p.x, cell, &okx), cell_of(p.y, cell, &oky), cell_of(p.z, cell, &okz)};
   if (!(okx && oky && okz && fabsf(p.x) <= mag && fabsf(p.y) <= mag && fabsf(p.z) <= mag)) {
     unresolved[i] = 1;  // not finite, beyond the coordinates the bounds hold for: brute-force semantics by the fallback
     return;
   }
   float best = 3.4e38f;
   int bi = 0;
-  for (int w = 0; w < nwide; ++w) {
-    const int t = wide_ids[w];
-    if (t < 0 || t >= nt) continue;
+  const auto test = [&](int t) {  // (an id outside the mesh is never read through)
+    if (t < 0 || t >= nt) return;
     const float *q = tris + (size_t)t * 9;
     pg_take(best, bi, point_triangle_d2(p, load3(q), load3(q + 3), load3(q + 6), min_area), t);
-  }
+  };
+  for (int w = 0; w < nwide; ++w) test(wide_ids[w]);
   bool done = ninc == 0;  // every triangle was wide: all of them have been tested
-  const float cmax = (float)max(max(abs(cx), abs(cy)), abs(cz)), pad = mag * PG_PAD_SCALE;
+  const float cmax = (float)max(max(abs(c[0]), abs(c[1])), abs(c[2])), pad = mag * PG_PAD_SCALE;
   for (int rho = 1; rho <= max_ring && !done; ++rho) {
-    const int z0 = max(cz - rho, -PG_KEY_HALF), z1 = min(cz + rho, PG_KEY_HALF - 1);
-    for (int x = max(cx - rho, -PG_KEY_HALF); x <= min(cx + rho, PG_KEY_HALF - 1); ++x)
-      for (int y = max(cy - rho, -PG_KEY_HALF); y <= min(cy + rho, PG_KEY_HALF - 1); ++y) {
-        // the cube of ring rho - 1 has been searched: of an inner column only the two end cells are new
-        const bool inner = rho > 1 && abs(x - cx) < rho && abs(y - cy) < rho;
-        for (int part = 0; part < (inner ? 2 : 1); ++part) {
-          const int za = inner ? (part ? cz + rho : cz - rho) : z0, zb = inner ? za : z1;
-          if (za < -PG_KEY_HALF || zb >= PG_KEY_HALF) continue;
-          const int s = pg_lower_bound(keys, 0, ninc, pg_key(x, y, za));
-          const int e = pg_lower_bound(keys, s, ninc, pg_key(x, y, zb) + 1);
-          for (int j = s; j < e; ++j) {
-            const int t = ids[j];
-            if (t < 0 || t >= nt) continue;
-            const float *q = tris + (size_t)t * 9;
-            pg_take(best, bi, point_triangle_d2(p, load3(q), load3(q + 3), load3(q + 6), min_area), t);
-          }
-        }
-      }
+    pg_ring_runs(keys, ninc, c, c, rho, [&](int s, int e) {  // (the point's cell as a box of one cell)
+      for (int j = s; j < e; ++j) test(ids[j]);
+    });
     done = pg_final(best, pg_reach(rho, cmax, cell, pad, shrink));
   }
   unresolved[i] = done ? 0 : 1;
@@ -258,18 +243,9 @@ __global__ __launch_bounds__(256) void pg_face_point_kernel(int ns, int nt, int 
   for (int rho = 1; rho <= max_ring && !done; ++rho) {
     const long long cols = (long long)(hi[0] - lo[0] + 1 + 2 * rho) * (hi[1] - lo[1] + 1 + 2 * rho);
     if (cols > max_cols) break;  // a broad box: the fallback walks the cloud
-    const int z0 = max(lo[2] - rho, -PG_KEY_HALF), z1 = min(hi[2] + rho, PG_KEY_HALF - 1);
-    for (int x = max(lo[0] - rho, -PG_KEY_HALF); x <= min(hi[0] + rho, PG_KEY_HALF - 1); ++x)
-      for (int y = max(lo[1] - rho, -PG_KEY_HALF); y <= min(hi[1] + rho, PG_KEY_HALF - 1); ++y) {
-        const bool inner = rho > 1 && x > lo[0] - rho && x < hi[0] + rho && y > lo[1] - rho && y < hi[1] + rho;
-        for (int part = 0; part < (inner ? 2 : 1); ++part) {
-          const int za = inner ? (part ? hi[2] + rho : lo[2] - rho) : z0, zb = inner ? za : z1;
-          if (za < -PG_KEY_HALF || zb >= PG_KEY_HALF) continue;
-          const int s = pg_lower_bound(keys, 0, ns, pg_key(x, y, za));
-          const int e = pg_lower_bound(keys, s, ns, pg_key(x, y, zb) + 1);
-          for (int j = s; j < e; ++j) pg_take(best, bi, point_triangle_d2(load3(spts + (size_t)j * 3), v0, v1, v2, min_area), order[j]);
-        }
-      }
+    pg_ring_runs(keys, ns, lo, hi, rho, [&](int s, int e) {
+      for (int j = s; j < e; ++j) pg_take(best, bi, point_triangle_d2(load3(spts + (size_t)j * 3), v0, v1, v2, min_area), order[j]);
+    });
     done = pg_final(best, pg_reach(rho, cmax, cell, pad, shrink));
   }
   unresolved[t] = done ? 0 : 1;
@@ -291,55 +267,33 @@ __device__ __forceinline__ void pg_wave_min(float &best, int &bi) {
   }
 }
 
-__global__ __launch_bounds__(256) void pg_point_face_subset_kernel(int nq, const int *__restrict__ qidx, int np, int nt,
-                                                                   const float *__restrict__ pts,
-                                                                   const float *__restrict__ tris, float min_area,
-                                                                   float *__restrict__ dist, int *__restrict__ idx) {
+// FACE_QUERY: the listed queries are triangles and the candidates the points; otherwise the other way round
+template <bool FACE_QUERY>
+__global__ __launch_bounds__(256) void pg_subset_kernel(int nq, const int *__restrict__ qidx, int np, int nt,
+                                                        const float *__restrict__ pts, const float *__restrict__ tris,
+                                                        float min_area, float *__restrict__ dist, int *__restrict__ idx) {
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= nq) return;
-  const int i = qidx[w];
-  if (i < 0 || i >= np) return;
-  const V3 p = load3(pts + (size_t)i * 3);
+  const int q = qidx[w];
+  if (q < 0 || q >= (FACE_QUERY ? nt : np)) return;
+  V3 p, v0, v1, v2;  // the query's own side is read once, the other per candidate
+  const auto point = [&](int i) { p = load3(pts + (size_t)i * 3); };
+  const auto face = [&](int t) { const float *f = tris + (size_t)t * 9; v0 = load3(f), v1 = load3(f + 3), v2 = load3(f + 6); };
+  if (FACE_QUERY) face(q); else point(q);
   float best = 3.4e38f;
   int bi = 0;
-  for (int t = lane_id(); t < nt; t += 64) {
-    const float *q = tris + (size_t)t * 9;
-    const float d = point_triangle_d2(p, load3(q), load3(q + 3), load3(q + 6), min_area);
+  for (int c = lane_id(); c < (FACE_QUERY ? np : nt); c += 64) {
+    if (FACE_QUERY) point(c); else face(c);
+    const float d = point_triangle_d2(p, v0, v1, v2, min_area);
     if (d < best) {
       best = d;
-      bi = t;
+      bi = c;
     }
   }
   pg_wave_min(best, bi);
   if (lane_id() == 0) {
-    dist[i] = best;
-    idx[i] = bi;
-  }
-}
-
-__global__ __launch_bounds__(256) void pg_face_point_subset_kernel(int nq, const int *__restrict__ qidx, int np, int nt,
-                                                                   const float *__restrict__ pts,
-                                                                   const float *__restrict__ tris, float min_area,
-                                                                   float *__restrict__ dist, int *__restrict__ idx) {
-  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= nq) return;
-  const int t = qidx[w];
-  if (t < 0 || t >= nt) return;
-  const float *q = tris + (size_t)t * 9;
-  const V3 v0 = load3(q), v1 = load3(q + 3), v2 = load3(q + 6);
-  float best = 3.4e38f;
-  int bi = 0;
-  for (int j = lane_id(); j < np; j += 64) {
-    const float d = point_triangle_d2(load3(pts + (size_t)j * 3), v0, v1, v2, min_area);
-    if (d < best) {
-      best = d;
-      bi = j;
-    }
-  }
-  pg_wave_min(best, bi);
-  if (lane_id() == 0) {
-    dist[t] = best;
-    idx[t] = bi;
+    dist[q] = best;
+    idx[q] = bi;
   }
 }
 
@@ -402,7 +356,7 @@ extern "C" int p2pb_p2m_grid_face_point(int ns, int nt, int nextra, int max_ring
 extern "C" int p2pb_p2m_point_face_subset(int nq, const int *qidx, int np, int nt, const float *points, const float *tris,
                                           float min_triangle_area, float *dist, int *idx, void *stream) {
   if (nq <= 0 || np <= 0 || nt <= 0 || !qidx || !points || !tris || !dist || !idx) return P2PB_EINVAL;
-  hipLaunchKernelGGL(pg_point_face_subset_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, nq, qidx, np, nt,
+  hipLaunchKernelGGL(pg_subset_kernel<false>, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, nq, qidx, np, nt,
                      points, tris, min_triangle_area, dist, idx);
   return p2pb_launch_status();
 }
@@ -410,7 +364,7 @@ extern "C" int p2pb_p2m_point_face_subset(int nq, const int *qidx, int np, int n
 extern "C" int p2pb_p2m_face_point_subset(int nq, const int *qidx, int np, int nt, const float *points, const float *tris,
                                           float min_triangle_area, float *dist, int *idx, void *stream) {
   if (nq <= 0 || np <= 0 || nt <= 0 || !qidx || !points || !tris || !dist || !idx) return P2PB_EINVAL;
-  hipLaunchKernelGGL(pg_face_point_subset_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, nq, qidx, np, nt,
+  hipLaunchKernelGGL(pg_subset_kernel<true>, dim3(cdiv(nq, 4)), dim3(256), 0, (hipStream_t)stream, nq, qidx, np, nt,
                      points, tris, min_triangle_area, dist, idx);
   return p2pb_launch_status();
 }

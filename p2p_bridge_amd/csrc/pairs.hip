@@ -13,6 +13,8 @@
 
 #include "common.h"
 
+#include "wave_topk.h"
+
 typedef unsigned long long u64;
 #define PAIRS_MAXK 128
 #define PAIRS_KNN_TILE 1024  // clean points of one LDS tile (12 KiB)
@@ -78,19 +80,9 @@ __global__ __launch_bounds__(256) void pairs_sample_mesh_kernel(int nverts, int 
 }
 
 // ---- k-NN ------------------------------------------------------------------------------------------------------------
-// A wave's K <= 128 best, as keys (distance bits << 32 | index: distances are >= 0, so the keys order like (distance, index))
-// ascending over ranks 0..127: lane l holds rank l in `a` and rank 64 + l in `b`, ~0 where empty. tau = the key of rank
-// K - 1, wave-uniform. v (wave-uniform, below tau, unlike every key of the list) goes in behind the keys below it.
-__device__ __forceinline__ void pairs_topk_insert(u64 &a, u64 &b, u64 &tau, u64 v, int k, int lane) {
-  const int pos = __popcll(__ballot(a < v)) + __popcll(__ballot(b < v));  // (< K: the key of rank K - 1 is tau > v)
-  const u64 a63 = __shfl(a, 63);
-  const u64 ua = __shfl_up(a, 1);
-  u64 ub = __shfl_up(b, 1);
-  if (lane == 0) ub = a63;
-  a = lane < pos ? a : (lane == pos ? v : ua);
-  b = lane + 64 < pos ? b : (lane + 64 == pos ? v : ub);
-  tau = k <= 64 ? __shfl(a, k - 1) : __shfl(b, k - 65);
-}
+// A wave's K <= 128 best, as keys (distance bits << 32 | index: distances are >= 0, so the keys order like (distance, index),
+// and no two are equal): wave_topk.h's list, two registers per lane.
+typedef WaveTopk<u64, PAIRS_MAXK / 64> PairsTopk;
 
 // One wave per query, PAIRS_KNN_WAVES queries of ONE patch per workgroup; the patch's clean points stream through LDS in tiles
 // of PAIRS_KNN_TILE (read once per workgroup, coalesced; a wave reads 64 consecutive points of the tile at a stride of three
@@ -112,7 +104,7 @@ __global__ __launch_bounds__(PAIRS_KNN_WAVES * 64) void pairs_knn_kernel(int s, 
     const float *qp = query + ((size_t)p * s + q) * 3;
     qx = qp[0], qy = qp[1], qz = qp[2];
   }
-  u64 a = ~0ull, b = ~0ull, tau = ~0ull;
+  PairsTopk best;
   for (int t0 = 0; t0 < m; t0 += PAIRS_KNN_TILE) {
     const int nt = min(PAIRS_KNN_TILE, m - t0);
     __syncthreads();  // (the previous tile has been read)
@@ -126,25 +118,17 @@ __global__ __launch_bounds__(PAIRS_KNN_WAVES * 64) void pairs_knn_kernel(int s, 
         const float d = sqdist3(tile[3 * j] - qx, tile[3 * j + 1] - qy, tile[3 * j + 2] - qz);
         c = ((u64)__float_as_uint(d) << 32) | (unsigned)(t0 + j);
       }
-      u64 todo = __ballot(c < tau);
-      while (todo) {
-        const int src = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const u64 v = __shfl(c, src);
-        if (v < tau) pairs_topk_insert(a, b, tau, v, k, lane);
-      }
+      best.offer(c, k, lane);
     }
   }
   if (!live) return;
   const size_t ob = ((size_t)p * s + q) * k;
-  if (lane < k) {
-    idx[ob + lane] = (int)(unsigned)a;
-    if (dist2) dist2[ob + lane] = __uint_as_float((unsigned)(a >> 32));
-  }
-  if (lane + 64 < k) {
-    idx[ob + 64 + lane] = (int)(unsigned)b;
-    if (dist2) dist2[ob + 64 + lane] = __uint_as_float((unsigned)(b >> 32));
-  }
+#pragma unroll
+  for (int i = 0; i < PAIRS_MAXK / 64; ++i)
+    if (64 * i + lane < k) {
+      idx[ob + 64 * i + lane] = (int)(unsigned)best.r[i];
+      if (dist2) dist2[ob + 64 * i + lane] = __uint_as_float((unsigned)(best.r[i] >> 32));
+    }
 }
 
 // ---- unique assignment -----------------------------------------------------------------------------------------------

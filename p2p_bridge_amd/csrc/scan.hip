@@ -3,14 +3,15 @@
 //   * back-projection of the valid pixels of a depth frame (fp64, one rounding);
 //   * voxel keys and per-voxel means (fp64 sums in a fixed order: sorted rows, no float atomics);
 //   * a uniform-grid neighbour search over SORTED CELL KEYS: the exact radius count and the exact k-th neighbour distance.
-// The grid is nothing but the reference points sorted by their packed cell key (torch sorts; memory O(n), whatever the
-// bounding box): the cells (cx, cy, cz0..cz1) of one column are consecutive keys, so one column of a query's neighbourhood
-// is ONE contiguous run of the sorted points, found by two binary searches on the sorted keys.
+// The grid -- cells, keys, the binary search, the run of one column, the bound of a ring -- is cell_grid.h's, the one
+// p2m_grid.hip searches; the wave's list of the k best is wave_topk.h's.
 // Contract: include/p2pb_hip.h, "scan fusion".
 #include "common.h"
 
-#define SCAN_KEY_HALF 1048576  // 2^20: cell indices lie in [-2^20, 2^20), three of them pack into 63 bits
-#define SCAN_BIG_CHUNK 4096    // rows of one workgroup of the large-voxel sum
+#include "cell_grid.h"
+#include "wave_topk.h"
+
+#define SCAN_BIG_CHUNK 4096  // rows of one workgroup of the large-voxel sum
 
 // ---- back-projection -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void scan_depth_valid_kernel(int npix, const float *__restrict__ depth, float zmin,
@@ -46,27 +47,15 @@ __global__ __launch_bounds__(256) void scan_backproject_kernel(int n, int width,
 }
 
 // ---- cell keys -------------------------------------------------------------------------------------------------------
-// the cell of a coordinate: floor of the IEEE fp32 quotient (so -0.001 lies in cell -1); *ok = false outside [-2^20, 2^20)
-// (NaN included). Monotone in p for a positive cell size: the neighbour search leans on that.
-__device__ __forceinline__ int scan_cell(float p, float cell, bool *ok) {
-  const float q = floorf(__fdiv_rn(p, cell));
-  *ok = q >= -(float)SCAN_KEY_HALF && q < (float)SCAN_KEY_HALF;
-  return *ok ? (int)q : 0;
-}
-
-__device__ __forceinline__ long long scan_key(int kx, int ky, int kz) {
-  return ((long long)(kx + SCAN_KEY_HALF) << 42) | ((long long)(ky + SCAN_KEY_HALF) << 21) | (long long)(kz + SCAN_KEY_HALF);
-}
-
 __global__ __launch_bounds__(256) void scan_cell_keys_kernel(int n, const float *__restrict__ xyz, float cell,
                                                              long long *__restrict__ keys, int *__restrict__ bad) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   bool okx, oky, okz;
-  const int kx = scan_cell(xyz[(size_t)i * 3], cell, &okx);
-  const int ky = scan_cell(xyz[(size_t)i * 3 + 1], cell, &oky);
-  const int kz = scan_cell(xyz[(size_t)i * 3 + 2], cell, &okz);
-  keys[i] = scan_key(kx, ky, kz);
+  const int kx = cell_of(xyz[(size_t)i * 3], cell, &okx);
+  const int ky = cell_of(xyz[(size_t)i * 3 + 1], cell, &oky);
+  const int kz = cell_of(xyz[(size_t)i * 3 + 2], cell, &okz);
+  keys[i] = cell_key(kx, ky, kz);
   if (!(okx && oky && okz)) *bad = 1;  // (every writer stores the same value)
 }
 
@@ -133,22 +122,6 @@ __global__ __launch_bounds__(256) void scan_segment_finish_kernel(int nbig, int 
 }
 
 // ---- the grid search -------------------------------------------------------------------------------------------------
-// first index in the ascending keys[0..n) whose key is >= key
-__device__ __forceinline__ int scan_lower_bound(const long long *__restrict__ keys, int n, long long key) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
-    if (keys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// the cell of a query coordinate, clamped to one cell beyond the key range (nothing lives there)
-__device__ __forceinline__ int scan_cell_clamped(float p, float cell) {
-  const float q = floorf(__fdiv_rn(p, cell));
-  return (int)fminf(fmaxf(q, -(float)SCAN_KEY_HALF - 1.0f), (float)SCAN_KEY_HALF);  // (NaN -> the lower clamp)
-}
-
 // counts[q] = min(limit, #{ j : sqdist3(p_j - q) <= r2 }) over the points sorted by cell key. One thread per query.
 // Which cells: every point that can pass the fp32 test has |p_a - q_a| <= reach on each axis (reach: the radius with the
 // roundings of the test added, computed by the caller), and the cell of a coordinate is monotone in the coordinate, so the
@@ -164,54 +137,38 @@ __global__ __launch_bounds__(256) void scan_radius_count_kernel(int nq, int n, c
   int lo[3], hi[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    lo[a] = max(scan_cell_clamped(nextafterf(qp[a] - reach, -INFINITY), cell), -SCAN_KEY_HALF);
-    hi[a] = min(scan_cell_clamped(nextafterf(qp[a] + reach, INFINITY), cell), SCAN_KEY_HALF - 1);
+    lo[a] = max(cell_clamped(nextafterf(qp[a] - reach, -INFINITY), cell), -CELL_KEY_HALF);
+    hi[a] = min(cell_clamped(nextafterf(qp[a] + reach, INFINITY), cell), CELL_KEY_HALF - 1);
   }
   int cnt = 0;
   if (lo[2] <= hi[2])
     for (int cx = lo[0]; cx <= hi[0] && cnt < limit; ++cx)
       for (int cy = lo[1]; cy <= hi[1] && cnt < limit; ++cy) {
-        const int s = scan_lower_bound(keys, n, scan_key(cx, cy, lo[2]));
-        const int e = scan_lower_bound(keys, n, scan_key(cx, cy, hi[2]) + 1);
+        int s, e;
+        cell_column(keys, n, cx, cy, lo[2], hi[2], s, e);
         for (int j = s; j < e && cnt < limit; ++j)
           cnt += sqdist3(pts[(size_t)j * 3] - qp[0], pts[(size_t)j * 3 + 1] - qp[1], pts[(size_t)j * 3 + 2] - qp[2]) <= r2;
       }
   counts[q] = cnt;
 }
 
-// The k smallest squared distances a wave has seen, ascending over lanes 0..k-1 (one value per lane, +inf where empty);
-// tau = the k-th (lane k-1), wave-uniform. Every lane offers one candidate d (+inf: none). Candidates below tau are inserted
-// one at a time behind their equals; after the first few steps of a stream almost none is.
-__device__ __forceinline__ void scan_topk_push(float &best, float &tau, float d, int k, int lane) {
-  unsigned long long m = __ballot(d < tau);
-  while (m) {
-    const int src = __ffsll((long long)m) - 1;
-    m &= m - 1;
-    const float v = __shfl(d, src);
-    if (v < tau) {
-      const int pos = __popcll(__ballot(best <= v));  // (< k: best[k-1] = tau > v)
-      const float up = __shfl_up(best, 1);
-      best = lane < pos ? best : (lane == pos ? v : up);
-      tau = __shfl(best, k - 1);
-    }
-  }
-}
+// the k <= 64 smallest squared distances a wave has seen, one per lane
+typedef WaveTopk<float, 1> ScanTopk;
 
 // offers the sorted points s..e to the wave's list
-__device__ __forceinline__ void scan_topk_run(float &best, float &tau, const float *__restrict__ pts, int s, int e, float qx,
-                                              float qy, float qz, int k, int lane) {
+__device__ __forceinline__ void scan_topk_run(ScanTopk &best, const float *__restrict__ pts, int s, int e, float qx, float qy,
+                                              float qz, int k, int lane) {
   for (int j0 = s; j0 < e; j0 += 64) {
     const int j = j0 + lane;
     float d = INFINITY;
     if (j < e) d = sqdist3(pts[(size_t)j * 3] - qx, pts[(size_t)j * 3 + 1] - qy, pts[(size_t)j * 3 + 2] - qz);
-    scan_topk_push(best, tau, d, k, lane);  // (NaN distances never enter: NaN < tau is false)
+    best.offer(d, k, lane);  // (NaN distances never enter: NaN < tau is false)
   }
 }
 
 // One wave per query qidx[w] (qidx NULL: query w). Ring rho = 1..max_ring: the cube of (2 rho + 1)^3 cells around the
 // query's cell, one column (2 rho + 1 cells along z = one run of the sorted points) per lane and binary-search pair, then the
-// runs one after the other, 64 points per step. Every point outside the cube lies in a cell at least rho + 1 away on some axis,
-// hence at least rho cell edges from the query, less the rounding of the two fp32 quotients (2^-23 of the cell index): the
+// runs one after the other, 64 points per step. Every point outside the cube is at least cell_ring_bound away: the
 // ring is final when the k-th best squared distance is no larger than that bound squared, which then holds for every
 // unvisited point's fp32 distance too (margins 1e-6 against the 2^-22 of sqdist3). out[q] = sqrt of it, unresolved[q] = 0;
 // otherwise unresolved[q] = 1 and out[q] is left alone. The list restarts with every ring (the cubes are nested).
@@ -226,40 +183,37 @@ __global__ __launch_bounds__(256) void scan_knn_grid_kernel(int nq, int n, int k
   const int q = qidx ? qidx[w] : w;
   const float qx = query[(size_t)q * 3], qy = query[(size_t)q * 3 + 1], qz = query[(size_t)q * 3 + 2];
   bool okx, oky, okz;
-  const int cx = scan_cell(qx, cell, &okx), cy = scan_cell(qy, cell, &oky), cz = scan_cell(qz, cell, &okz);
+  const int cx = cell_of(qx, cell, &okx), cy = cell_of(qy, cell, &oky), cz = cell_of(qz, cell, &okz);
   bool done = false;
-  float tau = INFINITY;
+  ScanTopk best;
   if (okx && oky && okz) {  // (a query outside the key range is nobody's neighbour cell: left to the next stage)
     const float cmax = (float)max(max(abs(cx), abs(cy)), abs(cz));
     for (int rho = 1; rho <= max_ring && !done; ++rho) {
-      float best = INFINITY;
-      tau = INFINITY;
+      best.clear();
       const int side = 2 * rho + 1, cols = side * side;
-      const int z0 = max(cz - rho, -SCAN_KEY_HALF), z1 = min(cz + rho, SCAN_KEY_HALF - 1);
+      const int z0 = max(cz - rho, -CELL_KEY_HALF), z1 = min(cz + rho, CELL_KEY_HALF - 1);
       for (int c0 = 0; c0 < cols; c0 += 64) {
         const int col = c0 + lane;
         int s = 0, e = 0;
         if (col < cols) {
           const int x = cx - rho + col / side, y = cy - rho + col % side;
-          if (x >= -SCAN_KEY_HALF && x < SCAN_KEY_HALF && y >= -SCAN_KEY_HALF && y < SCAN_KEY_HALF) {
-            s = scan_lower_bound(keys, n, scan_key(x, y, z0));
-            e = scan_lower_bound(keys, n, scan_key(x, y, z1) + 1);
-          }
+          if (x >= -CELL_KEY_HALF && x < CELL_KEY_HALF && y >= -CELL_KEY_HALF && y < CELL_KEY_HALF)
+            cell_column(keys, n, x, y, z0, z1, s, e);
         }
         unsigned long long live = __ballot(e > s);
         while (live) {
           const int l = __ffsll((long long)live) - 1;
           live &= live - 1;
-          scan_topk_run(best, tau, pts, __shfl(s, l), __shfl(e, l), qx, qy, qz, k, lane);
+          scan_topk_run(best, pts, __shfl(s, l), __shfl(e, l), qx, qy, qz, k, lane);
         }
       }
-      const float reach = ((float)rho - 1.1920929e-7f * (cmax + (float)rho + 2.0f)) * cell * 0.999999f;
-      done = reach > 0.0f && tau <= reach * reach * 0.999999f;
+      const float reach = cell_ring_bound(rho, cmax, cell);
+      done = reach > 0.0f && best.tau <= reach * reach * 0.999999f;
     }
   }
   if (lane == 0) {
     unresolved[q] = done ? 0 : 1;
-    if (done) out[q] = __fsqrt_rn(tau);
+    if (done) out[q] = __fsqrt_rn(best.tau);
   }
 }
 
@@ -272,9 +226,9 @@ __global__ __launch_bounds__(256) void scan_knn_brute_kernel(int nq, int n, int 
   if (w >= nq) return;
   const int lane = lane_id();
   const int q = qidx ? qidx[w] : w;
-  float best = INFINITY, tau = INFINITY;
-  scan_topk_run(best, tau, pts, 0, n, query[(size_t)q * 3], query[(size_t)q * 3 + 1], query[(size_t)q * 3 + 2], k, lane);
-  if (lane == 0) out[q] = __fsqrt_rn(tau);
+  ScanTopk best;
+  scan_topk_run(best, pts, 0, n, query[(size_t)q * 3], query[(size_t)q * 3 + 1], query[(size_t)q * 3 + 2], k, lane);
+  if (lane == 0) out[q] = __fsqrt_rn(best.tau);
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------

@@ -13,7 +13,7 @@ from typing import NamedTuple
 
 import torch
 
-KEY_HALF = 1 << 20  # p2pb_scan_cell_keys: cell indices in [-2^20, 2^20)
+from .cell_grid import KEY_HALF, sorted_cells  # (KEY_HALF: the planner's test holds the plan to the key range)
 INCIDENCES_PER_TRIANGLE = 8
 MAG_MIN, MAG_MAX = 1e-6, 1e6  # coordinates the kernels' fp32 bounds are argued for (no overflow in |cross|^2, no denormals)
 
@@ -210,15 +210,8 @@ class TriangleGrid:
             return (d, idx.long(), self._stats(T, T)) if return_stats else (d, idx.long())
         spts = order = skeys = extra = None
         if ns:
-            sub = points[sel].contiguous()
-            keys = torch.empty(ns, dtype=torch.int64, device=dev)
-            bad = torch.zeros(1, dtype=torch.int32, device=dev)
-            call("p2pb_scan_cell_keys", int(ns), ptr(sub), float(pl.cell), ptr(keys), ptr(bad), stream_ptr())
-            skeys, perm = torch.sort(keys)
-            spts = sub[perm].contiguous()
-            order = sel[perm].to(torch.int32).contiguous()
-            if int(bad) != 0:
-                raise RuntimeError("TriangleGrid: a point within the coordinate bound fell outside the key range")
+            spts, skeys, order = sorted_cells(points[sel].contiguous(), float(pl.cell), RuntimeError(
+                "TriangleGrid: a point within the coordinate bound fell outside the key range"), ids=sel.to(torch.int32))
         if nextra:
             extra = points[out_idx.long()].contiguous()
         d = torch.empty(T, dtype=torch.float32, device=dev)

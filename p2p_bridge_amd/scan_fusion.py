@@ -29,6 +29,7 @@ import os
 import numpy as np
 import torch
 
+from . import cell_grid
 from ._lib import ask, call, ptr, stream_ptr
 
 F32, F64, I32, I64, U8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
@@ -96,25 +97,19 @@ def backproject(image, depth, camera_to_world, intrinsic, min_depth=0.1, max_dep
 
 
 # ---- cell keys and the sorted grid -----------------------------------------------------------------------------------
-def _keys(xyz, cell, what):
-    """packed cell keys i64[n] of xyz f32[n,3] at cell edge fp32(cell); ValueError when a cell index leaves [-2^20, 2^20)"""
+def _cell(cell, what):
+    """-> (the cell edge as the kernels see it: fp32(cell), positive and finite; the ValueError for a cell index that leaves
+    [-2^20, 2^20))"""
     cell = float(np.float32(cell))
     if not (cell > 0.0 and math.isfinite(cell)):
         raise ValueError(f"{what}: cell size {cell} must be positive and finite")
-    n = xyz.shape[0]
-    keys = torch.empty(n, dtype=I64, device=xyz.device)
-    bad = torch.zeros(1, dtype=I32, device=xyz.device)
-    call("p2pb_scan_cell_keys", n, ptr(xyz), cell, ptr(keys), ptr(bad), stream_ptr())
-    if int(bad.item()):
-        raise ValueError(f"{what}: a coordinate is NaN or its cell index at size {cell} lies outside [-2^20, 2^20)")
-    return keys, cell
+    return cell, ValueError(f"{what}: a coordinate is NaN or its cell index at size {cell} lies outside [-2^20, 2^20)")
 
 
 def _grid(ref, cell, what):
     """-> (points sorted by cell key f32[n,3], sorted keys i64[n], the permutation i64[n], the cell edge as the kernels see it)"""
-    keys, cell = _keys(ref, cell, what)
-    skeys, perm = torch.sort(keys, stable=True)
-    return ref[perm].contiguous(), skeys, perm, cell
+    cell, refuse = _cell(cell, what)
+    return cell_grid.sorted_cells(ref, cell, refuse) + (cell,)
 
 
 # ---- voxel down-sampling ---------------------------------------------------------------------------------------------
@@ -133,8 +128,7 @@ def voxel_down_sample(xyz, voxel_size, *attrs):
             raise ValueError(f"attrs[{i}] must have at least one channel and live on the device of xyz")
     if n == 0:
         return (xyz.clone(),) + tuple(a.clone() for a in attrs)
-    keys, _ = _keys(xyz, voxel_size, "voxel_down_sample")
-    skeys, perm = torch.sort(keys, stable=True)
+    skeys, perm = torch.sort(cell_grid.cell_keys(xyz, *_cell(voxel_size, "voxel_down_sample")), stable=True)
     _, counts = torch.unique_consecutive(skeys, return_counts=True)
     m = counts.numel()
     starts = torch.zeros(m + 1, dtype=I64, device=xyz.device)

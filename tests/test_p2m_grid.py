@@ -63,6 +63,23 @@ def test_pair_function_is_stated_once():
         assert '#include "p2m_geom.h"' in open(os.path.join(csrc, f)).read()
 
 
+def test_cell_grid_and_wave_best_list_are_stated_once():
+    """the key packing and the cell quotient -- what the writers and the readers of sorted cell keys must agree on bit for
+    bit -- and the wave's sorted best list each live in one header that their users include"""
+    csrc = os.path.join(ROOT, "p2p_bridge_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    for needle in ("<< 42", "floorf(__fdiv_rn("):
+        assert [f for f, t in text.items() if needle in t] == ["cell_grid.h"], needle
+    for f in ("scan.hip", "p2m_grid.hip"):
+        assert '#include "cell_grid.h"' in text[f]
+    # the list's mark: a position counted by ballot, the shift by __shfl_up
+    lists = [f for f, t in text.items() if "__shfl_up(" in t and re.search(r"__popcll\(__ballot\([^;]*<=", t)]
+    assert lists == ["wave_topk.h"]
+    assert [f for f, t in text.items() if re.search(r"struct\s+WaveTopk\b", t)] == ["wave_topk.h"]
+    for f in ("scan.hip", "pairs.hip"):
+        assert '#include "wave_topk.h"' in text[f] and "WaveTopk<" in text[f]
+
+
 def test_method_argument_rejects_unknown_values():
     from p2p_bridge_amd import metrics as M
 

@@ -78,6 +78,32 @@ def test_icosphere_shell(M, area):
         assert torch.equal(d, d0) and torch.equal(i, i0)
 
 
+@pytest.mark.parametrize("u", [1.5, 2.5])
+@pytest.mark.parametrize("area", AREAS)
+def test_rings_two_and_three_resolve(M, area, u):
+    """Points u cell edges off the unit icosphere, 256 outside and 256 inside, u = 1.5 and u = 2.5: ring 1 alone resolves no
+    query in either direction (max_ring = 1 sends all of them to the fallback), the plan's rings resolve every one (no
+    fallback): the answers come out of the walk's "only the end cells of an inner column are new" branch, bit for bit."""
+    from test_metrics_unit_sphere_gpu import icosphere
+
+    verts, faces = icosphere(3)
+    tris = verts[faces].contiguous()
+    grid = M.TriangleGrid(tris.cuda(), area)
+    cell = grid.plan.cell
+    print(f"area={area} u={u}: cell={cell} max_ring={grid.plan.max_ring}")
+    g = torch.Generator().manual_seed(int(10 * u))
+    dirs = torch.nn.functional.normalize(torch.randn(512, 3, generator=g), dim=1)
+    radius = torch.cat([torch.full((256, 1), 1 + u * cell), torch.full((256, 1), 1 - u * cell)])
+    pts = (dirs * radius).contiguous()
+    out = check(M, pts, tris, area, grid)
+    print("rings:", out[0][2], out[1][2])
+    assert out[0][2]["fallback"] == 0 and out[1][2]["fallback"] == 0
+    grid.plan = grid.plan._replace(max_ring=1)
+    out = check(M, pts, tris, area, grid)
+    print("ring 1 only:", out[0][2], out[1][2])
+    assert out[0][2]["fallback"] == 512 and out[1][2]["fallback"] == 1280
+
+
 def _box_dist2(pts, tris):
     lo, hi = tris.min(dim=1).values, tris.max(dim=1).values  # [T,3]
     gap = torch.clamp(torch.maximum(lo[None] - pts[:, None], pts[:, None] - hi[None]), min=0)

@@ -126,6 +126,16 @@ def test_patch_knn_ties_and_offsets(clouds):
     _check_knn(clouds[0] + np.float32(50), [r + np.float32(50) for r in clouds[1]], 128, restated=False)  # the scene shifted
 
 
+@pytest.mark.parametrize("k", [64, 65])
+def test_patch_knn_at_the_second_register_of_the_list(k):
+    """K = 65 is the first list whose last rank, and with it tau, lives in the second register of a lane; K = 64 on the same
+    input is the last that does not. Patches of 70 points (barely above K) and 1100 (one crossing of the 1024-point LDS
+    tile); 5 queries: the second workgroup has three idle waves."""
+    rng = np.random.default_rng(13)
+    refs = [rng.uniform(-1, 1, (m, 3)).astype(np.float32) for m in (70, 1100)]
+    _check_knn(rng.uniform(-1, 1, (2, 5, 3)).astype(np.float32), refs, k, restated=False)
+
+
 def test_patch_knn_refuses_a_patch_smaller_than_k(clouds):
     query, refs = clouds
     with pytest.raises(ValueError):
