@@ -1113,6 +1113,28 @@ int p2pb_p2m_packed_backward(int kind, int np, int ns, const float *points, cons
                              const float *grad_dist, float min_triangle_area, const long long *order, const long long *start,
                              float *grad_points, float *grad_prims, void *stream);
 
+/* grid k-NN -------------------------------------------------------------------------------------------------------
+ * The K nearest points of a whole cloud WITH their indices, K <= 128: the (dist2, idx) of p2pb_knn_points, bit for bit and ties
+ * included, from the ring search of p2pb_scan_knn_grid (csrc/knn_grid.hip; Python side: p2p_bridge_amd/knn_grid.py; the tie and
+ * finality arguments: DESIGN.md, "Grid k-NN"). Pure additions like the p2pb_scan_* entry points: P2PB_ABI_VERSION stays 13.
+ * The grid is the one of "scan fusion": sorted_points f32[n,3] and sorted_keys i64[n] (keys of p2pb_scan_cell_keys at the edge
+ * `cell`, ascending), and rows i32[n] = the row of every sorted point in the caller's cloud. A wave keeps its K best as keys
+ * (bits of fma(dz,dz, fma(dy,dy, dx*dx)) << 32 | row), d = point - query: all different, ordered by (distance, index).
+ *
+ * p2pb_knn_grid: one wave per query qidx[w] (i32[nq]; NULL: query w), rings 1..max_ring (<= 16) of cells around the query's
+ *   cell. A ring is final when the K-th best squared distance is no larger than the squared distance to the nearest cell not
+ *   yet visited (roundings of the cell index allowed for, less a margin of 1e-6: no unvisited point can tie). Then dist2
+ *   f32[*,K] / idx i32[*,K] of row q hold the K pairs ascending and unresolved[q] = 0. Otherwise -- no final ring, fewer than K
+ *   points seen, a query cell outside the key range -- unresolved[q] = 1 and row q is not written.
+ * p2pb_knn_grid_brute: the same rows from a walk over all n points in the caller's order, one wave per query qidx[w].
+ * No atomics: the same inputs give the same bits.
+ * -> 0, P2PB_EINVAL for K outside [1, min(n, 128)], bad sizes or NULL operands (qidx may be NULL). */
+int p2pb_knn_grid(int nq, int n, int k, int max_ring, const int *qidx, const float *query, const float *sorted_points,
+                  const long long *sorted_keys, const int *rows, float cell, float *dist2, int *idx, unsigned char *unresolved,
+                  void *stream);
+int p2pb_knn_grid_brute(int nq, int n, int k, const int *qidx, const float *query, const float *points, float *dist2, int *idx,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

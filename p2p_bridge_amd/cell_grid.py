@@ -1,5 +1,6 @@
 """The host side of csrc/cell_grid.h: a cloud as a uniform grid = its points sorted by the packed key of their cell.
-Used by scan_fusion (radius counts, k-th neighbour distances, voxel keys) and p2m_grid (face -> point)."""
+Used by scan_fusion (radius counts, k-th neighbour distances, voxel keys), p2m_grid (face -> point) and knn_grid (k nearest
+neighbours with indices, through scan_fusion's grid helpers)."""
 import torch
 
 from ._lib import call, ptr, stream_ptr

@@ -1,7 +1,8 @@
-// cell_grid.h -- the uniform grid held as SORTED CELL KEYS, stated once for its two users: scan.hip (voxel keys, radius count,
-// k-th neighbour) and p2m_grid.hip (point <-> mesh search). The grid is nothing but a set of entries sorted by the packed key
-// of their cell (torch sorts; memory O(n), whatever the bounding box): the cells (x, y, z0..z1) of one column are consecutive
-// keys, so one column of a neighbourhood is ONE contiguous run of the sorted entries, found by two binary searches.
+// cell_grid.h -- the uniform grid held as SORTED CELL KEYS, stated once for its users: scan.hip (voxel keys, radius count,
+// k-th neighbour), p2m_grid.hip (point <-> mesh search) and knn_grid.hip (k nearest neighbours with indices). The grid is
+// nothing but a set of entries sorted by the packed key of their cell (torch sorts; memory O(n), whatever the bounding box):
+// the cells (x, y, z0..z1) of one column are consecutive keys, so one column of a neighbourhood is ONE contiguous run of the
+// sorted entries, found by two binary searches.
 // Whoever writes keys (p2pb_scan_cell_keys, p2pb_p2m_grid_fill) and whoever looks them up goes through these definitions, so
 // the two sides cannot drift apart. Key format: include/p2pb_hip.h, "scan fusion".
 #pragma once

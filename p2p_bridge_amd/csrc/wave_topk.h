@@ -1,7 +1,8 @@
 // wave_topk.h -- the k <= 64 R smallest keys a wave has seen, held in registers: rank 64 i + l lives in r[i] of lane l.
 // Invariants: ascending over ranks; empty = the type's maximum (+inf for float); tau = the key of rank k - 1, wave-uniform;
 // a candidate goes in behind its equals (position = the count of keys <= it), so equal keys stay in the order they came.
-// Users: scan.hip (squared distances, <float, 1>) and pairs.hip (distance bits << 32 | index, all different, <u64, 2>).
+// Users: scan.hip (squared distances, <float, 1>), pairs.hip (distance bits << 32 | index, all different, <u64, 2>) and
+// knn_grid.hip (the same keys over a whole cloud, <u64, 1> up to k = 64 and <u64, 2> above).
 #pragma once
 #include <limits>
 

@@ -21,9 +21,16 @@ F32, I32 = torch.float32, torch.int32
 _KNN = namedtuple("KNN", "dists idx knn")  # field names of pytorch3d.ops.knn._KNN
 
 
-def knn_points(p1, p2, K=1, return_nn=False):
+def knn_points(p1, p2, K=1, return_nn=False, method="brute"):
     """p1 f32[B,S,3] queries, p2 f32[B,N,3] -> KNN(dists f32[B,S,K] squared & ascending, idx i64[B,S,K],
-    knn f32[B,S,K,3] or None); ties by ascending index. csrc/knn.hip (radix select + LDS bitonic sort)."""
+    knn f32[B,S,K,3] or None); ties by ascending index. method "brute": csrc/knn.hip (radix select + LDS bitonic sort), one
+    workgroup per query over all N points, made for a few dozen queries with K a whole patch. method "grid" (opt-in, K <= 128):
+    the same tuple bit for bit from the ring search of knn_grid.PointGrid, one grid per batch element -- for many queries with
+    small K on a scan."""
+    if method not in ("brute", "grid"):
+        raise ValueError(f"knn_points: method {method!r} is neither 'brute' nor 'grid'")
+    if method == "grid" and int(K) > 128:
+        raise ValueError(f'knn_points: K={int(K)} exceeds 128, the limit of method="grid"; use method="brute"')
     check(p1, F32, "p1"), check(p2, F32, "p2")
     if p1.dim() != 3 or p2.dim() != 3 or p1.shape[2] != 3 or p2.shape[2] != 3 or p1.shape[0] != p2.shape[0]:
         raise ValueError("knn_points expects p1 [B,S,3] and p2 [B,N,3]")
@@ -33,6 +40,13 @@ def knn_points(p1, p2, K=1, return_nn=False):
     if not (1 <= k <= n) or k > 4096:
         raise ValueError(f"knn_points: K={k} must be in [1, min(N={n}, 4096)]")
     dev = p1.device
+    if method == "grid":
+        from .knn_grid import PointGrid
+
+        found = [PointGrid(p2[i], k).knn(p1[i], k) for i in range(b)]
+        dists, idx = torch.stack([f[0] for f in found]), torch.stack([f[1] for f in found])
+        nn = torch.gather(p2, 1, idx.reshape(b, s * k, 1).expand(b, s * k, 3)).reshape(b, s, k, 3) if return_nn else None
+        return _KNN(dists, idx, nn)
     dists = torch.empty(b, s, k, dtype=F32, device=dev)
     idx = torch.empty(b, s, k, dtype=I32, device=dev)
     nn = torch.empty(b, s, k, 3, dtype=F32, device=dev) if return_nn else None

@@ -31,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from ._lib import ask, call, ptr, stream_ptr
+from .knn_grid import PointGrid
 
 F16, F32, F64, I32, U8 = torch.float16, torch.float32, torch.float64, torch.int32, torch.uint8
 KNN_WS_BYTES = 1 << 30  # scratch of one p2pb_knn_points launch: the missing points are taken in chunks of this size
@@ -324,14 +325,9 @@ def _fill_cpu(feats, count, points, k):
     return 0
 
 
-def _fill_hip(feats, count, points, k):
-    n, c = feats.shape
-    dev = feats.device
-    missing = torch.nonzero(count == 0).flatten().to(I32)  # ascending
-    m = missing.numel()
-    if m == 0:
-        return 0
-    cloud = points.float().reshape(1, n, 3).contiguous()
+def _neighbours_hip(cloud, missing, k):
+    """the exhaustive search of csrc/knn.hip, the missing points taken in chunks of KNN_WS_BYTES of scratch -> i32[m,k]"""
+    n, m, dev = cloud.shape[1], missing.numel(), cloud.device
     nbr = torch.empty(m, k, dtype=I32, device=dev)
     step = max(1, min(m, KNN_WS_BYTES // (4 * n)))
     ws = torch.empty(int(ask("p2pb_knn_points_ws_bytes", 1, step, n)), dtype=U8, device=dev)
@@ -340,6 +336,21 @@ def _fill_hip(feats, count, points, k):
         query = cloud[0, missing[m0:m0 + s].long()].contiguous()
         call("p2pb_knn_points", 1, s, n, k, ptr(query), ptr(cloud),
              None, ptr(nbr[m0:m0 + s]), None, ptr(ws), stream_ptr())
+    return nbr
+
+
+def _fill_hip(feats, count, points, k, neighbours="brute"):
+    n, c = feats.shape
+    dev = feats.device
+    missing = torch.nonzero(count == 0).flatten().to(I32)  # ascending
+    m = missing.numel()
+    if m == 0:
+        return 0
+    cloud = points.float().reshape(1, n, 3).contiguous()
+    if neighbours == "grid":  # the same rows, bit for bit, from one ring search over the sorted cell-key grid
+        nbr = PointGrid(cloud[0], k)._search(cloud[0, missing.long()].contiguous(), k)[1]
+    else:
+        nbr = _neighbours_hip(cloud, missing, k)
     done_round = torch.zeros(n, dtype=I32, device=dev)
     remaining = torch.zeros(1, dtype=I32, device=dev)
     remaining += m
@@ -355,14 +366,18 @@ def _fill_hip(feats, count, points, k):
     return rounds
 
 
-def interpolate_missing_features(feats, count, points, k=10, return_rounds=False):
+def interpolate_missing_features(feats, count, points, k=10, return_rounds=False, neighbours="brute"):
     """Give every unobserved point (count == 0) the per-channel median of its neighbours (:282-326), IN PLACE.
     feats f16[N,C], count i32[N], points f32 or f64 [N,3] (neighbours are searched in fp32: csrc/knn.hip, ties by ascending
     index). The points are taken in ascending index; point i looks at its k nearest points of the whole cloud, keeps the rows
     that are not all-zero AT THAT MOMENT -- observed points, and unobserved points j < i with their filled rows -- and stores
     their median (mean of the two middle values for an even number, rounded to fp16 once), or zeros if none is left. On a GPU
     the in-place order runs as a wavefront of rounds (csrc/imgfeat.hip). Fewer than k points: ValueError.
+    neighbours "grid" (opt-in, CUDA only): the same neighbour rows from knn_grid.PointGrid instead of the exhaustive search --
+    the rounds are fed the same indices, so the result has the same bits. NaN or inf in points is then a ValueError.
     -> feats (with return_rounds: (feats, number of rounds; 0 on the CPU path))"""
+    if neighbours not in ("brute", "grid"):
+        raise ValueError(f"interpolate_missing_features: neighbours {neighbours!r} is neither 'brute' nor 'grid'")
     out = feats
     feats, count, points = _tensor(feats, "feats"), _tensor(count, "count"), _tensor(points, "points")
     dev = _one_device("interpolate_missing_features", feats, count, points)
@@ -379,7 +394,10 @@ def interpolate_missing_features(feats, count, points, k=10, return_rounds=False
         raise ValueError(f"interpolate_missing_features: {n} points, fewer than k={k}")
     if c < 1:
         raise ValueError("interpolate_missing_features: feats has no channels")
-    rounds = _fill_hip(feats, count, points, k) if dev.type == "cuda" else _fill_cpu(feats, count, points.float(), k)
+    if dev.type == "cuda":
+        rounds = _fill_hip(feats, count, points, k, neighbours)
+    else:
+        rounds = _fill_cpu(feats, count, points.float(), k)  # (its own exhaustive search: `neighbours` has nothing to choose)
     return (out, rounds) if return_rounds else out
 
 
@@ -395,7 +413,8 @@ def frame_stride(total, sampling_rate=5, autoskip=False):
 
 @torch.no_grad()
 def fuse_scene(points, frames, feature_type="rgb", feature_fn=None, batch_size=2, mask_size=(192, 256),
-               intrinsic_scale=256 / 1920, sampling_rate=5, autoskip=False, k=10, device=None, dino_from_grid=False):
+               intrinsic_scale=256 / 1920, sampling_rate=5, autoskip=False, k=10, device=None, dino_from_grid=False,
+               neighbours="brute"):
     """The per-scene loop of process_scene (:399-514) -> features f16[C,N'] (tensor on `device`), the transposed layout the
     data sets read; N' = the rows of `points` without NaN / inf (:403-405).
     points [N,3]; frames: a sequence of dicts {image f32[H,W,3] in [0,1], intrinsic 3x3 (full-resolution; rows 0-1 are scaled
@@ -405,7 +424,9 @@ def fuse_scene(points, frames, feature_type="rgb", feature_fn=None, batch_size=2
     own model), upsampled to (H, W) with F.interpolate(mode="bilinear") as :110 does. dino_from_grid=True (opt-in) never builds
     that [B,H,W,C] map: the token grid is sampled at the points' pixels (`update_features_from_grid`; fp32 evaluation of the
     fp16 grid, within one fp16 ulp of the map's values, so the features differ from the default path's in the last place).
-    device: default the device of `points` (cpu for numpy)."""
+    device: default the device of `points` (cpu for numpy). neighbours: interpolate_missing_features' ("grid": opt-in)."""
+    if neighbours not in ("brute", "grid"):
+        raise ValueError(f"fuse_scene: neighbours {neighbours!r} is neither 'brute' nor 'grid'")
     if feature_type not in ("rgb", "dino"):
         raise ValueError(f"fuse_scene: feature_type {feature_type!r} is neither 'rgb' nor 'dino'")
     if feature_type == "dino" and feature_fn is None:
@@ -449,7 +470,7 @@ def fuse_scene(points, frames, feature_type="rgb", feature_fn=None, batch_size=2
             mean = torch.zeros(n, maps.shape[-1], dtype=F16, device=dev)
             count = torch.zeros(n, dtype=I32, device=dev)
         update_features(mean, count, maps, valid, xy)
-    interpolate_missing_features(mean, count, points, k=k)
+    interpolate_missing_features(mean, count, points, k=k, neighbours=neighbours)
     return torch.nan_to_num(mean).t().contiguous()  # (:511-514)
 
 

@@ -187,17 +187,39 @@ def remove_radius_outliers(xyz, nb_points, search_radius, include_self=True):
 
 
 # ---- k-th neighbour distance -----------------------------------------------------------------------------------------
-def _knn_cell(ref, k):
+def _knn_cell(ref, k, what="knn_kth_distance"):
     """a first cell edge from the bounding box (k points per cell if the cloud filled it), and the smallest edge that keeps
     every key in range"""
     lo, hi = ref.min(0).values.double().cpu().numpy(), ref.max(0).values.double().cpu().numpy()
     if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
-        raise ValueError("knn_kth_distance: ref holds NaN or inf")
+        raise ValueError(f"{what}: ref holds NaN or inf")
     amax = float(max(np.abs(lo).max(), np.abs(hi).max()))
     floor = max(amax * 2.0 ** -19, 1e-30)
     ext = (hi - lo)[(hi - lo) > 0]
     cell = float((k * np.prod(ext) / ref.shape[0]) ** (1.0 / len(ext))) if len(ext) else 1.0
     return max(cell, floor), floor
+
+
+def _knn_fit(ref, k, what):
+    """the grid of ref (as _grid returns it) at a cell edge fitted to the density: the edge is moved, at most three times, until
+    the cell of the median point holds about k/2 points. Also knn_grid.PointGrid's."""
+    n, dev = ref.shape[0], ref.device
+    cell, floor = _knn_cell(ref, k, what)
+    target = max(k / 2.0, 2.0)
+    for it in range(4):
+        pts, skeys, perm, cell = _grid(ref, cell, what)
+        if it == 3:
+            break
+        counts = torch.unique_consecutive(skeys, return_counts=True)[1].sort().values
+        half = torch.searchsorted(torch.cumsum(counts, 0), torch.tensor([(n + 1) // 2], device=dev))
+        occ = float(counts[half.clamp(max=counts.numel() - 1)].item())  # points in the cell of the median point
+        if target / 2.0 <= occ <= target * 2.0:
+            break
+        step = min(8.0, max(0.125, (target / occ) ** 0.4))  # occupancy grows like cell^2 (surfaces) to cell^3
+        if cell * step < floor and cell <= floor * 1.0001:
+            break
+        cell = max(cell * step, floor)
+    return pts, skeys, perm, cell
 
 
 def knn_kth_distance(query, ref, k):
@@ -221,21 +243,7 @@ def knn_kth_distance(query, ref, k):
     out = torch.empty(nq, dtype=F32, device=dev)
     if nq == 0:
         return out
-    cell, floor = _knn_cell(ref, k)
-    target = max(k / 2.0, 2.0)
-    for it in range(4):
-        pts, skeys, _, cell = _grid(ref, cell, "knn_kth_distance")
-        if it == 3:
-            break
-        counts = torch.unique_consecutive(skeys, return_counts=True)[1].sort().values
-        half = torch.searchsorted(torch.cumsum(counts, 0), torch.tensor([(n + 1) // 2], device=dev))
-        occ = float(counts[half.clamp(max=counts.numel() - 1)].item())  # points in the cell of the median point
-        if target / 2.0 <= occ <= target * 2.0:
-            break
-        step = min(8.0, max(0.125, (target / occ) ** 0.4))  # occupancy grows like cell^2 (surfaces) to cell^3
-        if cell * step < floor and cell <= floor * 1.0001:
-            break
-        cell = max(cell * step, floor)
+    pts, skeys, _, cell = _knn_fit(ref, k, "knn_kth_distance")
     unresolved = torch.empty(nq, dtype=U8, device=dev)
     call("p2pb_scan_knn_grid", nq, n, k, KNN_RINGS, None, ptr(query),
          ptr(pts), ptr(skeys), cell, ptr(out), ptr(unresolved), stream_ptr())
