@@ -1135,6 +1135,25 @@ int p2pb_knn_grid(int nq, int n, int k, int max_ring, const int *qidx, const flo
 int p2pb_knn_grid_brute(int nq, int n, int k, const int *qidx, const float *query, const float *points, float *dist2, int *idx,
                         void *stream);
 
+/* grid nearest point -------------------------------------------------------------------------------------------------
+ * The ONE nearest point of a whole cloud with its index, for the 10^6 .. 10^7 queries of a room-size Chamfer distance: row q
+ * of p2pb_knn_grid at K = 1, and the (dist, idx) of p2pb_chamfer_forward's nm_distance_kernel, bit for bit and ties included
+ * (the lowest row among the nearest), from the same ring search over the same grid (csrc/nn_grid.hip; Python side:
+ * p2p_bridge_amd/knn_grid.py, PointGrid.nearest; the arguments: DESIGN.md, "Grid nearest point / Chamfer"). A pure addition:
+ * P2PB_ABI_VERSION stays 13. sorted_points, sorted_keys, rows, cell: as for "grid k-NN".
+ *
+ * p2pb_nn_grid: one LANE per query qidx[w] (i32[nq]; NULL: query w), rings 1..max_ring (<= 16) of cells around the query's
+ *   cell, one running minimum of the keys (bits of fma(dz,dz, fma(dy,dy, dx*dx)) << 32 | row), d = point - query. A ring is
+ *   final by p2pb_knn_grid's test with the best distance in the K-th's place. Then dist2[q] f32 / idx[q] i32 hold the pair and
+ *   unresolved[q] = 0. Otherwise -- no final ring, nothing seen, a query cell outside the key range -- unresolved[q] = 1 and
+ *   dist2[q] / idx[q] are not written. The lanes are independent: the order of qidx decides which queries share a wave (give
+ *   it a spatially coherent one, neighbouring lanes then read the same lines) and cannot change a bit of the result.
+ * No atomics: the same inputs give the same bits.
+ * -> 0, P2PB_EINVAL for bad sizes or NULL operands (qidx may be NULL). */
+int p2pb_nn_grid(int nq, int n, int max_ring, const int *qidx, const float *query, const float *sorted_points,
+                 const long long *sorted_keys, const int *rows, float cell, float *dist2, int *idx, unsigned char *unresolved,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

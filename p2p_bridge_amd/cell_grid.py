@@ -1,6 +1,6 @@
 """The host side of csrc/cell_grid.h: a cloud as a uniform grid = its points sorted by the packed key of their cell.
 Used by scan_fusion (radius counts, k-th neighbour distances, voxel keys), p2m_grid (face -> point) and knn_grid (k nearest
-neighbours with indices, through scan_fusion's grid helpers)."""
+neighbours with indices, through scan_fusion's grid helpers; the lane order of its nearest-point queries)."""
 import torch
 
 from ._lib import call, ptr, stream_ptr
@@ -23,6 +23,19 @@ def cell_keys(xyz, cell, refuse):
     if int(bad.item()):
         raise refuse
     return keys
+
+
+def query_order(xyz, cell):
+    """the rows of xyz f32[n,3] (n >= 1) sorted by their cell key at the edge `cell`, i32[n]: neighbours in this order are
+    neighbours in space, which is all the order is for (knn_grid.PointGrid.nearest). Rows with a NaN or a cell index outside
+    the key range go last; equal keys keep their order"""
+    keys, _ = _keys(xyz, cell)
+    # the quotient of cell_grid.h (a tensor divisor: torch multiplies by the reciprocal of a plain number). A quotient that
+    # differed by an ulp would only move a row within the order
+    quot = torch.floor(xyz / torch.full((1,), cell, dtype=xyz.dtype, device=xyz.device))
+    inside = ((quot >= -float(KEY_HALF)) & (quot < float(KEY_HALF))).all(1)
+    keys = torch.where(inside, keys, torch.full_like(keys, torch.iinfo(torch.int64).max))
+    return torch.sort(keys, stable=True)[1].to(torch.int32)
 
 
 def sorted_cells(xyz, cell, refuse, ids=None):

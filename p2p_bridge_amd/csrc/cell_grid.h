@@ -1,5 +1,6 @@
 // cell_grid.h -- the uniform grid held as SORTED CELL KEYS, stated once for its users: scan.hip (voxel keys, radius count,
-// k-th neighbour), p2m_grid.hip (point <-> mesh search) and knn_grid.hip (k nearest neighbours with indices). The grid is
+// k-th neighbour), p2m_grid.hip (point <-> mesh search), knn_grid.hip (k nearest neighbours with indices) and nn_grid.hip
+// (the nearest point, one lane per query). The grid is
 // nothing but a set of entries sorted by the packed key of their cell (torch sorts; memory O(n), whatever the bounding box):
 // the cells (x, y, z0..z1) of one column are consecutive keys, so one column of a neighbourhood is ONE contiguous run of the
 // sorted entries, found by two binary searches.

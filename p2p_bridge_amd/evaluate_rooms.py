@@ -31,6 +31,8 @@ from . import metrics as M
 
 MULTIPLIER = 10 ** 3
 P2M_METHOD_DEFAULT = "grid"  # --p2m_method when absent (same numbers either way; timing: profiles/p2m_grid_room_timing.txt)
+CD_METHODS = ("brute", "grid")
+CD_METHOD_DEFAULT = "brute"  # --cd_method when absent (same numbers either way; timing: profiles/nn_grid_timing.txt)
 _PLY_RGB = ("red", "green", "blue")
 COLUMNS = ["model_config", "point_dist", "face_dist", "cd_pred_gt", "cd_gt_pred"]
 _PLY_TYPES = {"char": "b", "int8": "b", "uchar": "B", "uint8": "B", "short": "h", "int16": "h", "ushort": "H", "uint16": "H",
@@ -151,11 +153,28 @@ def build_mesh_index(args, gt_mesh):
                                 torch.as_tensor(gt_mesh["faces"]).long().cuda(), normalize=bool(_ns(args, "normalize")))
 
 
+def _cd_method(args):
+    method = _ns(args, "cd_method") or CD_METHOD_DEFAULT
+    if method not in CD_METHODS:
+        raise ValueError(f"cd_method must be one of {CD_METHODS}, got {method!r}")
+    return method
+
+
+def build_cloud_index(args, gt):
+    """the PointGrid of a scene's ground-truth cloud, normalised or raw as args.normalize says (None: brute-force Chamfer):
+    built once, handed to every get_mectrics call of that scene as `ref_grid`"""
+    if gt is None or _cd_method(args) != "grid":
+        return None
+    return M.cloud_point_grid(torch.as_tensor(np.asarray(gt)).float().cuda(), normalize=bool(_ns(args, "normalize")))
+
+
 @torch.no_grad()
-def get_mectrics(args, gt, pred, gt_mesh=None, mesh_index=None) -> dict:
-    """args.dataset in {snpp, arkit}, args.normalize, args.p2m_method in {grid, brute} (absent: P2M_METHOD_DEFAULT); gt /
-    pred: clouds [N,3]; gt_mesh: {"points", "faces"} (snpp); mesh_index: build_mesh_index(args, gt_mesh), built here if
-    absent. Both methods return the same floats."""
+def get_mectrics(args, gt, pred, gt_mesh=None, mesh_index=None, ref_grid=None) -> dict:
+    """args.dataset in {snpp, arkit}, args.normalize, args.p2m_method in {grid, brute} (absent: P2M_METHOD_DEFAULT),
+    args.cd_method in {brute, grid} (absent: CD_METHOD_DEFAULT); gt / pred: clouds [N,3]; gt_mesh: {"points", "faces"} (snpp);
+    mesh_index: build_mesh_index(args, gt_mesh), ref_grid: build_cloud_index(args, gt), each built here if absent. Both
+    methods of either choice return the same floats."""
+    cd_method = _cd_method(args)
     dev = "cuda"
     gt = torch.as_tensor(np.asarray(gt)).float().to(dev)
     pred = torch.as_tensor(np.asarray(pred)).float().to(dev)
@@ -172,7 +191,8 @@ def get_mectrics(args, gt, pred, gt_mesh=None, mesh_index=None) -> dict:
         data["point_dist"], data["face_dist"] = pd * MULTIPLIER, fd * MULTIPLIER
     if pred.ndim == 2:
         pred, gt = pred.unsqueeze(0), gt.unsqueeze(0)
-    a, b = M.cd_unit_sphere(pred.contiguous(), gt.contiguous(), normalize=bool(_ns(args, "normalize")))
+    a, b = M.cd_unit_sphere(pred.contiguous(), gt.contiguous(), normalize=bool(_ns(args, "normalize")), method=cd_method,
+                            ref_grid=ref_grid if cd_method == "grid" else None)
     data["cd_pred_gt"], data["cd_gt_pred"] = a * MULTIPLIER, b * MULTIPLIER
     return data
 
@@ -184,7 +204,10 @@ def calculate_model_metrics(data: Dict, model_name: str, args) -> Dict:
     preds = data["models"][model_name]
     if preds and "mesh_index" not in data:  # once per scene, for every model and prediction of it
         data["mesh_index"] = build_mesh_index(args, data["faro_mesh"])
-    return {cfg: get_mectrics(args, data["faro"], pred, gt_mesh=data["faro_mesh"], mesh_index=data.get("mesh_index"))
+    if preds and "cloud_index" not in data:
+        data["cloud_index"] = build_cloud_index(args, data["faro"])
+    return {cfg: get_mectrics(args, data["faro"], pred, gt_mesh=data["faro_mesh"], mesh_index=data.get("mesh_index"),
+                              ref_grid=data.get("cloud_index"))
             for cfg, pred in preds.items()}
 
 
@@ -260,7 +283,7 @@ def handle_scene(scene_folder: str, args) -> None:
         torch.cuda.empty_cache()
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--data_root", type=str, required=True)
     ap.add_argument("--seed", type=int, default=42)
@@ -270,7 +293,13 @@ def main(argv=None):
     ap.add_argument("--suffix", default="")
     ap.add_argument("--p2m_method", choices=["grid", "brute"], default=P2M_METHOD_DEFAULT,
                     help="point-to-mesh search: exact grid (csrc/p2m_grid.hip) or every pair (csrc/p2m.hip); same numbers")
-    args = ap.parse_args(argv)
+    ap.add_argument("--cd_method", choices=list(CD_METHODS), default=CD_METHOD_DEFAULT,
+                    help="Chamfer search: every pair (csrc/chamfer.hip) or exact grid (csrc/nn_grid.hip); same numbers")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     for f in os.listdir(args.data_root):
         handle_scene(os.path.join(args.data_root, f), args)
 

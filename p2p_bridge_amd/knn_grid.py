@@ -3,6 +3,8 @@ of cell_grid.py. The room-size form of denoise.knn_points (csrc/knn.hip: one wor
 
     PointGrid(ref, k_hint, cell=None)        the grid of one reference cloud, built once
     PointGrid.knn(query, k)                  -> (dist2 f32[nq,k] ascending, idx i64[nq,k]), ties by ascending index
+    PointGrid.nearest(query, order=None)     -> (dist2 f32[nq], idx i64[nq]): knn(query, 1) from csrc/nn_grid.hip, one lane
+                                             per query; the room-size form of csrc/chamfer.hip (metrics.chamfer_grid)
     knn(query, ref, k, cell=None)            the one-shot form
 
 The results are those of p2pb_knn_points bit for bit, ties included: both keep the k smallest keys (bits of sqdist3 << 32 |
@@ -12,6 +14,7 @@ grid; what is left repeats on grids 4x and 16x coarser (isolated points); the re
 count and pair threshold are scan_fusion.knn_kth_distance's. CUDA tensors only: there is no CPU path."""
 import torch
 
+from . import cell_grid
 from ._lib import call, ptr, stream_ptr
 from .scan_fusion import KNN_BRUTE_PAIRS, KNN_LEVELS, KNN_RINGS, _cuda, _grid, _knn_fit
 
@@ -99,6 +102,56 @@ class PointGrid:
         return_stats also {"ring": [queries resolved by the rings of each level], "brute": queries left to the full walk}.
         1 <= k <= min(n, 128), whatever k_hint was (it only sets the cell edge)."""
         dist2, idx, stats = self._search(query, k)
+        return (dist2, idx.long(), stats) if return_stats else (dist2, idx.long())
+
+    def _nearest(self, query, order):
+        """-> dist2 f32[nq], idx i32[nq], stats. order: None, or an i32 permutation of the queries that the CALLER answers
+        for (an index outside [0, nq) would be followed)"""
+        _cuda(query, F32, (None, 3), "query")
+        ref = self.ref
+        if query.device != ref.device:
+            raise RuntimeError("PointGrid.nearest: query and ref must be on one device")
+        nq, n, dev = query.shape[0], ref.shape[0], ref.device
+        dist2 = torch.empty(nq, dtype=F32, device=dev)
+        idx = torch.empty(nq, dtype=I32, device=dev)
+        stats = {"ring": [0] * KNN_LEVELS, "brute": 0}
+        if nq == 0:
+            return dist2, idx, stats
+        unresolved = torch.empty(nq, dtype=U8, device=dev)
+        left = cell_grid.query_order(query, self.cell) if order is None else order  # the queries still open, in lane order
+        for lv in range(KNN_LEVELS):
+            pts, skeys, rows, cell = self.level(lv)
+            open_ = left.numel()
+            call("p2pb_nn_grid", open_, n, KNN_RINGS, ptr(left), ptr(query), ptr(pts), ptr(skeys), ptr(rows), cell, ptr(dist2),
+                 ptr(idx), ptr(unresolved), stream_ptr())
+            left = left[unresolved[left.long()] != 0].contiguous()
+            stats["ring"][lv] = open_ - left.numel()
+            if left.numel() == 0 or left.numel() * n <= KNN_BRUTE_PAIRS:
+                break
+        if left.numel():
+            call("p2pb_knn_grid_brute", left.numel(), n, 1, ptr(left), ptr(query), ptr(ref), ptr(dist2), ptr(idx), stream_ptr())
+            stats["brute"] = left.numel()
+        return dist2, idx, stats
+
+    def nearest(self, query, order=None, return_stats=False):
+        """query f32[nq,3] -> (dist2 f32[nq], idx i64[nq]): knn(query, 1) with the last axis squeezed, bit for bit (the lowest
+        row among equally near points), from csrc/nn_grid.hip: one lane per query and one running minimum instead of a wave
+        and its best-list. Stages and stats as knn. order: an i32[nq] permutation of the queries that decides only which
+        queries sit in neighbouring lanes -- not a bit of the result depends on it; None: the queries sorted by their cell key
+        at this grid's edge (those outside the key range last). Hand in a spatially coherent one where it is already at hand,
+        such as the sorted rows of the queries' own PointGrid."""
+        if order is not None:
+            _cuda(query, F32, (None, 3), "query")
+            nq = query.shape[0]
+            _cuda(order, I32, (nq,), "order")
+            if order.device != self.ref.device:
+                raise RuntimeError("PointGrid.nearest: order and ref must be on one device")
+            rows = order.long()
+            seen = torch.zeros(nq + 1, dtype=torch.bool, device=order.device)  # (slot nq: the rows outside [0, nq))
+            seen[torch.where((rows < 0) | (rows >= nq), nq, rows)] = True
+            if bool(seen[nq]) or not bool(seen[:nq].all()):
+                raise ValueError("PointGrid.nearest: order must be a permutation of the query rows")
+        dist2, idx, stats = self._nearest(query, order)
         return (dist2, idx.long(), stats) if return_stats else (dist2, idx.long())
 
 

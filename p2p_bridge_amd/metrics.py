@@ -230,14 +230,80 @@ def denormalize_pcl(pc, center, scale):
     return pc * scale + center
 
 
+_CD_METHODS = ("brute", "grid")
+CHAMFER_GRID_K_HINT = 1  # PointGrid's k_hint for chamfer_grid: the cell of the median point holds about two points
+
+
+def _cloud_grid(grid, xyz, b, what):
+    """the PointGrid of one cloud of a chamfer_grid call: the caller's (B = 1, checked against the cloud) or one built here"""
+    from .knn_grid import PointGrid
+
+    if grid is None:
+        return PointGrid(xyz[b], CHAMFER_GRID_K_HINT)
+    if xyz.shape[0] != 1:
+        raise ValueError(f"{what}: a prebuilt grid goes with batch size 1")
+    if not isinstance(grid, PointGrid) or grid.ref.shape != xyz[0].shape or grid.ref.device != xyz.device or \
+            not torch.equal(grid.ref, xyz[0]):
+        raise ValueError(f"{what} was built for another cloud")
+    return grid
+
+
+def chamfer_grid(xyz1, xyz2, grid1=None, grid2=None):
+    """xyz1 f32[B,N,3], xyz2 f32[B,M,3] (CUDA) -> (dist1 f32[B,N], dist2 f32[B,M], idx1 i32[B,N], idx2 i32[B,M]): the four
+    tensors of chamfer_3DDist()(xyz1, xyz2), bit for bit, from the exact grid search of csrc/nn_grid.hip instead of every
+    pair: the room-size form (10^6 points and more per cloud). One knn_grid.PointGrid per cloud and batch row, fitted with
+    k_hint = CHAMFER_GRID_K_HINT; each cloud's queries go out in the order of its OWN grid's sorted rows, so neighbouring
+    lanes search neighbouring cells. grid1 / grid2: PointGrids of xyz1[0] / xyz2[0] built earlier (B = 1 only), for a cloud
+    that is scored against many.
+    No gradient: runs under no_grad and raises RuntimeError if an input requires grad -- the differentiable path stays
+    chamfer_3DDist. NaN or inf coordinates (and cell indices beyond the key range) raise the grid's ValueError, where the brute
+    force returns its inf / index-0 rows."""
+    if xyz1.requires_grad or xyz2.requires_grad:
+        raise RuntimeError("chamfer_grid has no gradient: use chamfer_3DDist for inputs that require grad")
+    with torch.no_grad():
+        xyz1, xyz2 = xyz1.float().contiguous(), xyz2.float().contiguous()
+        if xyz1.dim() != 3 or xyz2.dim() != 3 or xyz1.shape[2] != 3 or xyz2.shape[2] != 3 or xyz1.shape[0] != xyz2.shape[0]:
+            raise ValueError(f"chamfer_grid: xyz1 [B,N,3] and xyz2 [B,M,3], got {list(xyz1.shape)} and {list(xyz2.shape)}")
+        b, n, m, dev = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1], xyz1.device
+        dist1, dist2 = torch.empty(b, n, device=dev), torch.empty(b, m, device=dev)
+        idx1 = torch.empty(b, n, dtype=torch.int32, device=dev)
+        idx2 = torch.empty(b, m, dtype=torch.int32, device=dev)
+        for i in range(b):
+            g1, g2 = _cloud_grid(grid1, xyz1, i, "grid1"), _cloud_grid(grid2, xyz2, i, "grid2")
+            dist1[i], idx1[i], _ = g2._nearest(xyz1[i], g1.level(0)[2])
+            dist2[i], idx2[i], _ = g1._nearest(xyz2[i], g2.level(0)[2])
+        return dist1, dist2, idx1, idx2
+
+
 @torch.no_grad()
-def cd_unit_sphere(gen, ref, normalize=True):
-    """(mean_i min_j, mean_j min_i) squared distances, gen/ref [B,N,3] (metrics/metrics.py:177-195)"""
+def cd_unit_sphere(gen, ref, normalize=True, method="brute", ref_grid=None):
+    """(mean_i min_j, mean_j min_i) squared distances, gen/ref [B,N,3] (metrics/metrics.py:177-195). method="grid": the same
+    two floats from chamfer_grid (room-size clouds); ref_grid: the PointGrid of the normalised (normalize=True) or raw ref[0],
+    built earlier (B = 1), for a ground truth that many predictions are scored against."""
+    if method not in _CD_METHODS:
+        raise ValueError(f"method must be one of {_CD_METHODS}, got {method!r}")
+    if ref_grid is not None and method != "grid":
+        raise ValueError("a ref_grid goes with method='grid'")
     if normalize:
         ref, center, scale = normalize_sphere(ref)
         gen = normalize_pcl(gen, center, scale)
-    cd1, cd2 = chamfer_dist_nograd(gen.contiguous(), ref.contiguous())
+    if method == "grid":
+        cd1, cd2 = chamfer_grid(gen.contiguous(), ref.contiguous(), grid2=ref_grid)[:2]
+    else:
+        cd1, cd2 = chamfer_dist_nograd(gen.contiguous(), ref.contiguous())
     return cd1.mean().item(), cd2.mean().item()
+
+
+@torch.no_grad()
+def cloud_point_grid(ref, normalize=True):
+    """the PointGrid that cd_unit_sphere(gen, ref[None], normalize, method="grid", ref_grid=...) accepts, ref f32[N,3]: built
+    once per ground-truth cloud, reused for every prediction scored against it"""
+    from .knn_grid import PointGrid
+
+    ref = ref.float().cuda()
+    if normalize:
+        ref = normalize_sphere(ref.unsqueeze(0))[0][0]
+    return PointGrid(ref.contiguous(), CHAMFER_GRID_K_HINT)
 
 
 def chamfer_distance_unit_sphere(gen, ref, batch_reduction="mean", point_reduction="mean"):
